@@ -4,6 +4,8 @@
 (BASELINE.json configs[1]), synthetic audio resident in HBM, recipe (random-init) weights.
 
     python bench.py [--gpus N --steps K --warmup W]                 configs[1] (default)
+    python bench.py ... --full                       adds roofline, roofline_conv, cpu_baseline
+    python bench.py ... --dump-outputs DIR           the last timed step's outputs as DIR/*.npy
     python bench.py --batch 64 --n-codebooks 32                      configs[2] shape
     python bench.py --sweep [--batch 16]                             configs[4]: VBR level sweep
     python bench.py --gpus N ...          N ranks (this script launches torch.distributed.run)
@@ -12,7 +14,9 @@
 Multi-GPU: clips shard data-parallel (each rank its own clips, no data-path collective), weak
 scaling; the timed region is bracketed by barrier + synchronize and the MAX over ranks is
 reported; the sweep's [audio seconds, bits, frames] are SUM-reduced over ranks (RCCL) so its
-bpf / kbps are job-wide. Rank 0 prints one JSON line, including
+bpf / kbps are job-wide. Rank 0 prints one JSON line: the headline figure (value, ms_per_step)
+and the workload's description. A plain run does nothing beyond set-up, warm-up and the timed
+steps; with --full the line also carries
   roofline      the RVQ path (torch.ops.vrvq.rvq_encode: one fused launch of projection ->
                 chain -> expansion) against HBM, bytes per SURVEY.md §8(d), per-launch durations from HIP events
                 recorded on the launch stream inside the timed steps; per-kernel split from the
@@ -245,6 +249,49 @@ def cpu_baseline(kwargs, clips: int, runs: int = 3):
                       f"median of {runs} runs ({', '.join(f'{t:.2f}' for t in ts)} s)"}
 
 
+DUMP_BUDGET = 64 * 10 ** 6  # bytes of .npy payload one --dump-outputs run may write
+
+
+def named_outputs(out, prefix: str = ""):
+    """(name, tensor) pairs of what a step returned: a tensor, a number, or dicts / sequences
+    of them (None entries dropped); nested names are joined with '_'."""
+    if out is None:
+        return []
+    if isinstance(out, dict):
+        items = [(str(k), v) for k, v in out.items()]
+    elif isinstance(out, (list, tuple)):
+        items = [(str(i), v) for i, v in enumerate(out)]
+    else:
+        return [(prefix or "output", torch.as_tensor(out))]
+    pairs = []
+    for k, v in items:
+        k = "".join(c if c.isalnum() or c in "-." else "_" for c in k)
+        pairs += named_outputs(v, f"{prefix}_{k}" if prefix else k)
+    return pairs
+
+
+def dump_outputs(out, path: str, suffix: str = "") -> None:
+    """Write a step's outputs as path/<name><suffix>.npy: floating tensors as float32 (float64
+    stays), integer and bool tensors as float64 (exact). Over DUMP_BUDGET in all, every array
+    keeps the same fraction of its elements: a fixed sample (seed 0, sorted flat indices)."""
+    os.makedirs(path, exist_ok=True)
+    pairs = named_outputs(out)
+
+    def width(t):
+        return 4 if t.is_floating_point() and t.dtype != torch.float64 else 8
+
+    total = sum(t.numel() * width(t) for _, t in pairs)
+    frac = min(1.0, 0.99 * DUMP_BUDGET / max(total, 1))
+    for name, t in pairs:
+        t = t.detach()
+        if frac < 1.0:
+            keep = max(1, int(t.numel() * frac))
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), keep, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float32 if width(t) == 4 else torch.float64).cpu().numpy()
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+
+
 def build_model(args, dev):
     import vrvq_amd
     from vrvq_amd.recipe import load_recipe
@@ -254,6 +301,69 @@ def build_model(args, dev):
     model = vrvq_amd.DAC_VRVQ(**kwargs)
     load_recipe(model, seed=0)
     return model.to(dev).eval(), kwargs
+
+
+def rooflines(args, model, timer: RvqTimer, ms_per_step: float, clip: int, n_levels: int) -> dict:
+    """--full: the roofline and roofline_conv entries of the result line, from the launch
+    timing `timer` collected inside the timed steps."""
+    import vrvq_amd
+    nq = args.n_codebooks
+    T = math.ceil(clip / model.hop_length)
+    rvq_ms = timer.mean_ms()
+    kern_ms, kern_n, per_call = timer.kernel_ms()
+    from_part = vrvq_amd.model.RVQ_PROJ
+    byt = rvq_bytes(args.batch, T, nq, from_partials=from_part)
+    # the dominant kernel's time per rvq_encode call (the fused launches of the call: one per 32
+    # clips); the operator bracket when the shape takes the three launches (no kernel-attached
+    # events there)
+    dur_ms = kern_ms * per_call if kern_n else rvq_ms
+    achieved = byt / (dur_ms * 1e-3) / 1e9
+    fl_enc, fl_dec = conv_flops(model, args.batch, T * model.hop_length)
+    flops = fl_enc + (n_levels if args.sweep else 1) * fl_dec
+    conv_ms = ms_per_step - rvq_ms
+    conv_tflops = flops / (conv_ms * 1e-3) / 1e12
+    shape = ({(32, 8): False, (64, 32): True}.get((args.batch, nq))
+             if not args.sweep and clip == CLIP_SAMPLES else None)
+    traffic, traffic_src = rvq_pmc_traffic(shape) if shape is not None else (None, None)
+    split, split_src = rvq_kernel_split(shape) if shape is not None else (None, None)
+    return {
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     "kernel": ("RVQ path: one torch.ops.vrvq.rvq_encode_part = "
+                                "rvq_pt_kernel per group of resident clips (chain parts sum "
+                                "the 8 channel-split in_proj partials the encoder's last conv "
+                                "wrote in its epilogue, vrvq_conv1d_proj, then the stage "
+                                "chain; expansion workgroups with a loader wave write z_q_is "
+                                "/ z_q; in-launch tagged-granule hand-offs)"
+                                if from_part else
+                                "RVQ path: torch.ops.vrvq.rvq_encode on channel-major z = "
+                                "rvq_fused_kernel per <= 32 clips at T <= 96, else three "
+                                "launches (A/B path, VRVQ_RVQ_PROJ=0)"),
+                     "bytes_per_call": byt,
+                     "bytes_model": ("SURVEY.md §8(d) with the kernel's input = the 8 "
+                                     "channel-split in_proj partials (8 x 8 nq fp32 per "
+                                     "frame) instead of z, W_in not read"
+                                     if from_part else "SURVEY.md §8(d)"),
+                     "bytes_per_call_survey_z_input": rvq_bytes(args.batch, T, nq,
+                                                                from_partials=False),
+                     "kernel_us": round(kern_ms * 1e3, 2) if kern_n else None,
+                     "kernel_launches_timed": kern_n,
+                     "launches_per_call": round(per_call, 3),
+                     "path_us": round(rvq_ms * 1e3, 2),
+                     "kernel_us_rocprof": split, "kernel_us_source": split_src},
+        "roofline_conv": {"bound": "mfma", "achieved": round(conv_tflops, 2),
+                          "peak": round(X3_PEAK_TFLOPS, 1), "unit": "TFLOP/s",
+                          "frac": round(conv_tflops / X3_PEAK_TFLOPS, 4),
+                          "flops_per_step": flops,
+                          "note": "algorithmic fp32 conv FLOPs / (step time - RVQ launches) "
+                                  "against the x3 ceiling: every MFMA conv runs the x3 path "
+                                  "(csrc/conv_x3.h: both operands split exactly into 3 bf16 "
+                                  "terms, 6 bf16 MFMAs per fp32 product pair, fp32 "
+                                  "accumulate -- fp32-accurate), whose ceiling is the bf16 "
+                                  "dense peak / 6 = 419.4 TF/s; the fp32-input MFMA peak "
+                                  "(157.3 TF/s) is not this path's bound"},
+    }
 
 
 TRAIN_CLIP = 16758  # conf/dataset.yml train duration 0.38 s at 44.1 kHz
@@ -280,6 +390,8 @@ def train_main(args, world: int, rank: int, dev):
     res_t = timed_steps(step, args.steps, args.warmup, sync=torch.cuda.synchronize, device=dev)
     ms = res_t.seconds / args.steps * 1e3
     value = throughput(args.batch * TRAIN_CLIP / SR, res_t)
+    if args.dump_outputs:
+        dump_outputs(res_t.last, args.dump_outputs, f".rank{rank}" if world > 1 else "")
     losses = {k: round(float(v), 5) for k, v in res_t.last.items()}
     ranks_seen = int(sum_over_ranks([1.0], dev)[0])
     if rank == 0:
@@ -360,12 +472,18 @@ def main(argv=None):
                          "1-s clips, inference.py:69's 12 levels for longer clips)")
     ap.add_argument("--max-decode-clips", type=int, default=None,
                     help="sweep: decode the levels' z_q in batches of at most this many clips")
+    ap.add_argument("--full", action="store_true",
+                    help="also report roofline (RVQ launch timing inside the timed steps), "
+                         "roofline_conv and cpu_baseline; off: only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--train", action="store_true",
                     help="configs[3]: vrvq_a2 training step (generator + discriminator + losses, "
                          "DDP over RCCL), 0.38 s clips")
     ap.add_argument("--cpu-clips", type=int, default=32,
                     help="clips of the cpu_baseline sample (BASELINE.md: the full B=32 batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the cpu_baseline leg out")
     ap.add_argument("--selftest", action="store_true",
                     help="launcher / timing self-test: gloo on CPU with a stub step, no GPU")
     args = ap.parse_args(argv)
@@ -406,8 +524,11 @@ def main(argv=None):
     model, kwargs = build_model(args, dev)
     audio = torch.from_numpy(synthetic_audio(args.batch, clip,
                                              seed=shard_seed(1234, rank))).to(dev)
-    timer = RvqTimer()
-    timer.install()
+    timer = None
+    if args.full:  # the roofline's launch timing: event pairs around every RVQ call
+        timer = RvqTimer()
+        timer.install()
+    timing = {"on": False}
     nq = args.n_codebooks
     fps = math.floor(SR / model.hop_length)
     lvl_ev = {"all": []}
@@ -431,7 +552,7 @@ def main(argv=None):
                                for i in range(0, z_all.shape[0], cap)])
                 bpfs = [vrvq_amd.ops.bpf(m, bits) for m in masks]
                 e1.record()
-                if timer.enabled:
+                if timing["on"]:
                     lvl_ev["all"].append((e0, e1))
                 B = args.batch
                 return [(lv, masks[i], bpfs[i], y[i * B:(i + 1) * B])
@@ -442,28 +563,26 @@ def main(argv=None):
                 return model(audio, SR, None, args.level)
 
     def on():
-        timer.start()
+        timing["on"] = True
+        if timer is not None:
+            timer.start()
 
     def off():
-        timer.stop()
+        timing["on"] = False
+        if timer is not None:
+            timer.stop()
 
     res_t = timed_steps(step, args.steps, args.warmup, sync=torch.cuda.synchronize, device=dev,
                         on_start=on, on_stop=off)
     vrvq_amd.check_errors(dev)  # end of work: a timed-out RVQ hand-off raises here, not silently
     ms_per_step = res_t.seconds / args.steps * 1e3
     value = throughput(args.batch * clip / SR, res_t)
-    T = math.ceil(clip / model.hop_length)
-    rvq_ms = timer.mean_ms()
-    kern_ms, kern_n, per_call = timer.kernel_ms()
-    from_part = vrvq_amd.model.RVQ_PROJ
-    byt = rvq_bytes(args.batch, T, nq, from_partials=from_part)
-    # the dominant kernel's time per rvq_encode call (the fused launches of the call: one per 32
-    # clips); the operator bracket when the shape takes the three launches (no kernel-attached
-    # events there)
-    dur_ms = kern_ms * per_call if kern_n else rvq_ms
-    achieved = byt / (dur_ms * 1e-3) / 1e9
-    fl_enc, fl_dec = conv_flops(model, args.batch, T * model.hop_length)
-    flops = fl_enc + (len(levels) if args.sweep else 1) * fl_dec
+    if args.dump_outputs:
+        last = res_t.last
+        if args.sweep:
+            last = {f"level{i}": {"mask": m, "bpf": b, "audio": y}
+                    for i, (_lv, m, b, y) in enumerate(last)}
+        dump_outputs(last, args.dump_outputs, f".rank{rank}" if world > 1 else "")
     levels_rep = None
     if args.sweep:
         levels_rep = []
@@ -476,12 +595,6 @@ def main(argv=None):
                                "decode_ms_all_levels_rank0": round(ms, 3),
                                "decode_audio_sec_per_s_all_levels": round(
                                    len(levels) * rep.audio_seconds / (ms * 1e-3), 2)})
-    conv_ms = ms_per_step - rvq_ms
-    conv_tflops = flops / (conv_ms * 1e-3) / 1e12
-    shape = ({(32, 8): False, (64, 32): True}.get((args.batch, nq))
-             if not args.sweep and clip == CLIP_SAMPLES else None)
-    traffic, traffic_src = rvq_pmc_traffic(shape) if shape is not None else (None, None)
-    split, split_src = rvq_kernel_split(shape) if shape is not None else (None, None)
     ranks_seen = int(sum_over_ranks([1.0], dev)[0])
     if rank == 0:
         lv_txt = ",".join(f"{v:g}" for v in levels)
@@ -509,46 +622,12 @@ def main(argv=None):
                        "global_batch": args.batch * world, "clip_samples": clip,
                        "n_codebooks": nq,
                        "parallelism": f"dp{world} (replicas, no data-path collective)"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": ("RVQ path: one torch.ops.vrvq.rvq_encode_part = "
-                                    "rvq_pt_kernel per group of resident clips (chain parts sum "
-                                    "the 8 channel-split in_proj partials the encoder's last conv "
-                                    "wrote in its epilogue, vrvq_conv1d_proj, then the stage "
-                                    "chain; expansion workgroups with a loader wave write z_q_is "
-                                    "/ z_q; in-launch tagged-granule hand-offs)"
-                                    if from_part else
-                                    "RVQ path: torch.ops.vrvq.rvq_encode on channel-major z = "
-                                    "rvq_fused_kernel per <= 32 clips at T <= 96, else three "
-                                    "launches (A/B path, VRVQ_RVQ_PROJ=0)"),
-                         "bytes_per_call": byt,
-                         "bytes_model": ("SURVEY.md §8(d) with the kernel's input = the 8 "
-                                         "channel-split in_proj partials (8 x 8 nq fp32 per "
-                                         "frame) instead of z, W_in not read"
-                                         if from_part else "SURVEY.md §8(d)"),
-                         "bytes_per_call_survey_z_input": rvq_bytes(args.batch, T, nq,
-                                                                    from_partials=False),
-                         "kernel_us": round(kern_ms * 1e3, 2) if kern_n else None,
-                         "kernel_launches_timed": kern_n,
-                         "launches_per_call": round(per_call, 3),
-                         "path_us": round(rvq_ms * 1e3, 2),
-                         "kernel_us_rocprof": split, "kernel_us_source": split_src},
-            "roofline_conv": {"bound": "mfma", "achieved": round(conv_tflops, 2),
-                              "peak": round(X3_PEAK_TFLOPS, 1), "unit": "TFLOP/s",
-                              "frac": round(conv_tflops / X3_PEAK_TFLOPS, 4),
-                              "flops_per_step": flops,
-                              "note": "algorithmic fp32 conv FLOPs / (step time - RVQ launches) "
-                                      "against the x3 ceiling: every MFMA conv runs the x3 path "
-                                      "(csrc/conv_x3.h: both operands split exactly into 3 bf16 "
-                                      "terms, 6 bf16 MFMAs per fp32 product pair, fp32 "
-                                      "accumulate -- fp32-accurate), whose ceiling is the bf16 "
-                                      "dense peak / 6 = 419.4 TF/s; the fp32-input MFMA peak "
-                                      "(157.3 TF/s) is not this path's bound"},
         }
+        if args.full:
+            res.update(rooflines(args, model, timer, ms_per_step, clip, len(levels)))
         if levels_rep is not None:
             res["levels"] = levels_rep
-        if world == 1 and not args.no_cpu_baseline and not args.sweep:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.sweep:
             res["cpu_baseline"] = cpu_baseline(kwargs, args.cpu_clips)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -32,6 +32,9 @@ import torch  # noqa: E402
 
 from vrvq_amd.recipe import recipe_state_dict, shapes_of, synthetic_audio  # noqa: E402
 
+sys.path.insert(0, HERE)
+from golden_io import save_golden  # noqa: E402  (splits a fixture over 1 MiB into parts)
+
 LEVELS = [0.25, 0.5, 1.0, 2.0]
 MASK_KAT_S = [0.0, 1.0, 2.0, 7.0, 8.0, -0.5, 3.9999999, 4.5, 27.0, 31.9999]
 
@@ -156,7 +159,7 @@ def model_fixture(DAC, ref_utils, kw, batch, name, manifest, n_quantizers=None, 
     res["audio_out"] = fwd["audio"].numpy()
     if model.model_type == "VBR" and n_quantizers is None:
         res.update(sweep(model, ref_utils, xp, enc, model.n_codebooks))
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
+    save_golden(HERE, name, res)
     imp = enc.get("imp_map")
     manifest[name] = {
         "kwargs": kw, "batch": batch, "length": 44100, "audio_seed": 1234, "weight_seed": 0,
@@ -186,7 +189,7 @@ def rvq_stress_fixture(DAC, kw, name, manifest, batch=4, frames=50, seed=7):
            "imp_map": enc["imp_map"].numpy(), "mask_imp": enc["mask_imp"].numpy(),
            "commitment_loss": np.float32(enc["commitment_loss"].item()),
            "z_q_is_norm": enc["z_q_is"].norm(dim=(2, 3)).numpy()}
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
+    save_golden(HERE, name, res)
     manifest[name] = {"kwargs": kw, "batch": batch, "frames": frames, "z_seed": seed,
                       "weight_seed": 0, "min_top2_gap_per_stage": gaps,
                       "state_dict": {k: list(v.shape) for k, v in model.state_dict().items()}}
@@ -219,7 +222,7 @@ def from_codes_fixture(DAC, kw, name, manifest, batch=2, frames=40, seed=5, vbr=
             res["mask"] = mask.numpy()
         audio = model.decode(z_q)
     res.update(z_q=z_q.numpy(), z_p=z_p.numpy(), z_q_is=z_q_is.numpy(), audio=audio.numpy())
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
+    save_golden(HERE, name, res)
     manifest[name] = {"kwargs": kw, "batch": batch, "frames": frames, "codes_seed": seed,
                       "weight_seed": 0, "vbr": vbr,
                       "state_dict": {k: list(v.shape) for k, v in model.state_dict().items()}}
@@ -250,7 +253,7 @@ def from_latents_fixture(DAC, kw, name, manifest, batch=2, frames=40, seed=21):
             z_q, z_p, codes = q.from_latents(lat)
         res.update({f"{tag}_latents": lat.numpy(), f"{tag}_z_q": z_q.numpy(),
                     f"{tag}_z_p": z_p.numpy(), f"{tag}_codes": codes.numpy()})
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
+    save_golden(HERE, name, res)
     manifest[name] = {"kwargs": kw, "batch": batch, "frames": frames, "latents_seed": seed,
                       "weight_seed": 0,
                       "state_dict": {k: list(v.shape) for k, v in model.state_dict().items()}}
@@ -336,7 +339,7 @@ def train_fixture(DAC, kw, name, manifest, batch, seed, length=16758, audio_seed
             res["g_full/" + pname] = g.float().numpy()
         else:
             res["g_s/" + pname] = g[torch.from_numpy(grad_sample_index(g.numel()))].float().numpy()
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **res)
+    save_golden(HERE, name, res)
     n_full = int(batch * model.quantizer.full_codebook_rate)
     n_drop = int(batch * model.quantizer.quantizer_dropout)
     manifest[name] = {"kwargs": kw, "batch": batch, "length": length, "audio_seed": audio_seed,

@@ -21,7 +21,7 @@ while IFS= read -r c; do
   done
 done <<< "$CASES"
 if [ "${BENCH:-0}" = 1 ]; then
-  run bench_A 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-  run bench_B 300 env $B_ENV python bench.py --steps 20 --warmup 3 --no-cpu-baseline
+  run bench_A 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+  run bench_B 300 env $B_ENV python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
 fi
 exit 0

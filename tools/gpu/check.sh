@@ -14,10 +14,10 @@ run() { local name=$1 to=$2; shift 2
 has() { [[ " $STEPS " == *" $1 "* ]]; }
 has smoke && run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
 has tests && run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -rf --timeout 120 --timeout-method thread ${PYTEST_ARGS}
-has bench && run bench 500 python bench.py --steps 20 --warmup 3
-has benchq && run benchq 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-has cfg3 && run cfg3 300 python bench.py --batch 64 --n-codebooks 32 --steps 10 --warmup 3 --no-cpu-baseline
-has sweep && run sweep 300 python bench.py --sweep --steps 10 --warmup 3
+has bench && run bench 500 python bench.py --full --steps 20 --warmup 3
+has benchq && run benchq 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+has cfg3 && run cfg3 300 python bench.py --full --batch 64 --n-codebooks 32 --steps 10 --warmup 3 --no-cpu-baseline
+has sweep && run sweep 300 python bench.py --full --sweep --steps 10 --warmup 3
 has rvq && run rvq_b32 120 python tools/rvq_bench.py && run rvq_b64 120 python tools/rvq_bench.py --batch 64 --nq 32
 has rvqprof && run rvq_prof 200 rocprofv3 --kernel-trace --stats -d gpurun_out/rvqprof_$TAG -o run --output-format csv -- python tools/rvq_bench.py --iters 20
 has rvqpmc && { TAG=${TAG} bash tools/gpu/pmc_rvq.sh || exit 1; }

@@ -15,6 +15,6 @@ for c in "384 5568" "768 696"; do set -- $c
   done
 done
 run tests_B 300 env VRVQ_CONV_K1X3_192=1 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_parity.py -k "x3 or conv1d or fixture"
-run bench_A 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-run bench_B 300 env VRVQ_CONV_K1X3_192=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
+run bench_A 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+run bench_B 300 env VRVQ_CONV_K1X3_192=1 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
 exit 0

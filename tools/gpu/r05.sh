@@ -21,15 +21,15 @@ has rvqtests && run rvq_tests 700 $PT tests/test_gpu_parity.py -k "rvq or golden
 has rvqb && run rvq_b32 180 python tools/rvq_bench.py --batch 32 --nq 8 --variants 3
 has rvqb && run rvq_b64 180 python tools/rvq_bench.py --batch 64 --nq 32 --variants 3 --paths fm,2
 has stamps && TAIL=45 run stamps 120 python tools/rvq_fused_stamps.py --fm
-has bench && run bench 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-has benchab && run bench_noplanes 300 env VRVQ_CONV_PLANES=0 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-has benchfull && run benchfull 500 python bench.py
-has cfg3 && run cfg3 300 python bench.py --batch 64 --n-codebooks 32 --steps 10 --warmup 2 --no-cpu-baseline
-has sweep && run sweep 300 python bench.py --sweep --steps 10 --warmup 2 --no-cpu-baseline
+has bench && run bench 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+has benchab && run bench_noplanes 300 env VRVQ_CONV_PLANES=0 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+has benchfull && run benchfull 500 python bench.py --full
+has cfg3 && run cfg3 300 python bench.py --full --batch 64 --n-codebooks 32 --steps 10 --warmup 2 --no-cpu-baseline
+has sweep && run sweep 300 python bench.py --full --sweep --steps 10 --warmup 2 --no-cpu-baseline
 has rvqprof && run rvqprof 200 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG}_rvq -o run --output-format csv -- python tools/rvq_bench.py --batch 32 --nq 8 --iters 20 --paths fm
 has prof && run prof 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG} -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline
 has profnp && run profnp 300 env VRVQ_CONV_PLANES=0 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG}_np -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline
 has long && run long_tests 500 $PT tests/test_gpu_long_clip.py
-has bench10 && run bench10 400 python bench.py --clip-seconds 10 --batch 1 --sweep --steps 5 --warmup 2 --no-cpu-baseline
+has bench10 && run bench10 400 python bench.py --full --clip-seconds 10 --batch 1 --sweep --steps 5 --warmup 2 --no-cpu-baseline
 has all && run gpu_tests 1000 $PT tests -m gpu
 exit 0

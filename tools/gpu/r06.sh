@@ -24,12 +24,12 @@ has rvqb && run rvq_b64 180 python tools/rvq_bench.py --batch 64 --nq 32 --varia
 has rvqb10 && run rvq_b1x10 180 python tools/rvq_bench.py --batch 1 --frames 862 --nq 8 --variants 3 --paths pt,2
 has stamps && TAIL=50 run stamps 120 python tools/rvq_fused_stamps.py --pt
 
-has bench && run bench 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-has benchz && run benchz 300 env VRVQ_RVQ_PROJ=0 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-has benchfull && run benchfull 500 python bench.py
-has cfg3 && run cfg3 300 python bench.py --batch 64 --n-codebooks 32 --steps 10 --warmup 2 --no-cpu-baseline
-has sweep && run sweep 300 python bench.py --sweep --steps 10 --warmup 2 --no-cpu-baseline
-has bench10 && run bench10 400 python bench.py --clip-seconds 10 --batch 1 --sweep --steps 5 --warmup 2 --no-cpu-baseline
+has bench && run bench 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+has benchz && run benchz 300 env VRVQ_RVQ_PROJ=0 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+has benchfull && run benchfull 500 python bench.py --full
+has cfg3 && run cfg3 300 python bench.py --full --batch 64 --n-codebooks 32 --steps 10 --warmup 2 --no-cpu-baseline
+has sweep && run sweep 300 python bench.py --full --sweep --steps 10 --warmup 2 --no-cpu-baseline
+has bench10 && run bench10 400 python bench.py --full --clip-seconds 10 --batch 1 --sweep --steps 5 --warmup 2 --no-cpu-baseline
 has train && run train 400 python bench.py --train --steps 3 --warmup 2
 has rvqprof && run rvqprof 200 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG}_rvq -o run --output-format csv -- python tools/rvq_bench.py --batch 32 --nq 8 --iters 20 --paths pt
 has rvqprof3 && run rvqprof3 200 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG}_cfg3_rvq -o run --output-format csv -- python tools/rvq_bench.py --batch 64 --nq 32 --iters 20 --paths pt

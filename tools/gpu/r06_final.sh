@@ -12,10 +12,10 @@ run() { local name=$1 to=$2; shift 2
 has() { [[ " ${STEPS:-smoke all bench prof} " == *" $1 "* ]]; }
 has smoke && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 has all && run gpu_tests 900 python -u -m pytest -x -q -rf --timeout 120 --timeout-method thread tests -m gpu
-has bench && run bench 400 python bench.py --steps 20 --warmup 5
+has bench && run bench 400 python bench.py --full --steps 20 --warmup 5
 has prof && run prof 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG} -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline
-has cfg3 && run cfg3 300 python bench.py --batch 64 --n-codebooks 32 --steps 10 --warmup 2 --no-cpu-baseline
-has sweep && run sweep 300 python bench.py --sweep --steps 10 --warmup 2 --no-cpu-baseline
+has cfg3 && run cfg3 300 python bench.py --full --batch 64 --n-codebooks 32 --steps 10 --warmup 2 --no-cpu-baseline
+has sweep && run sweep 300 python bench.py --full --sweep --steps 10 --warmup 2 --no-cpu-baseline
 has train && run train 400 python bench.py --train --steps 3 --warmup 2
-has bench10 && run bench10 400 python bench.py --clip-seconds 10 --batch 1 --sweep --steps 5 --warmup 2 --no-cpu-baseline
+has bench10 && run bench10 400 python bench.py --full --clip-seconds 10 --batch 1 --sweep --steps 5 --warmup 2 --no-cpu-baseline
 exit 0

@@ -20,7 +20,7 @@ for rep in 1 2; do
     r=$(timeout -k 10 120 python tools/rvq_bench.py --paths pt --iters 50 2>&1 | grep "^path") || { echo "FAIL"; exit 1; }
     echo "rep $rep $c iso: $r" | tee -a $OUT
     if [ -z "$NOSTEP" ]; then
-      r=$(timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1) || { echo "FAIL"; exit 1; }
+      r=$(timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1) || { echo "FAIL"; exit 1; }
       echo "rep $rep $c step: $(echo $r | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(d["value"], r["kernel_us"], r["frac"])')" | tee -a $OUT
     fi
   done

@@ -28,8 +28,8 @@ for c in "384 384 5568" "256 256 5568" "768 768 696" "512 512 696"; do set -- $c
 done
 run st_128_A 60 python tools/conv_bench.py --x3 --cin 128 --cout 256 --t 5568 --k 8 --stride 4
 run st_128_SB 60 env $B_ENV python tools/conv_bench.py --x3 --cin 128 --cout 256 --t 5568 --k 8 --stride 4
-run bench_SB 300 env $B_ENV python bench.py --steps 20 --warmup 3 --no-cpu-baseline
+run bench_SB 300 env $B_ENV python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
 run test_B 300 env VRVQ_RU_BN64=1 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_parity.py -k "residual_unit or fixture or golden"
-run bench_A 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
-run bench_B 300 env VRVQ_RU_BN64=1 python bench.py --steps 20 --warmup 3 --no-cpu-baseline
+run bench_A 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
+run bench_B 300 env VRVQ_RU_BN64=1 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
 exit 0

@@ -11,7 +11,7 @@ run() { local name=$1 to=$2; shift 2
   if [ $rc -ne 0 ]; then echo "STOP after $name (rc=$rc)"; tail -20 "gpurun_out/${TAG}_$name.log"; exit $rc; fi; return 0; }
 PT="python -u -m pytest -x -q -rf --timeout 120 --timeout-method thread"
 run tests 600 $PT tests/test_gpu_parity.py -k "residual or x3 or model_forward or config2 or batch_invariance or golden"
-B="python bench.py --steps 20 --warmup 3 --no-cpu-baseline"
+B="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline"
 run b1 300 env VRVQ_RU_P2H=1 $B
 run b0 300 env VRVQ_RU_P2H=0 $B
 run b1b 300 env VRVQ_RU_P2H=1 $B

@@ -10,7 +10,7 @@ run() { local name=$1 to=$2; shift 2
   if [ $rc -ne 0 ]; then echo "STOP after $name (rc=$rc)"; exit $rc; fi; return 0; }
 for rep in 1 2; do
   for v in "f64_96_128_256" "f64_96_256" "f64_128_256" "f64_256" "f96_128_256"; do
-    run ${v}_$rep 300 env VRVQ_RU_FUSED=$(echo ${v#f} | tr _ ,) python bench.py --steps 20 --warmup 3 --no-cpu-baseline
+    run ${v}_$rep 300 env VRVQ_RU_FUSED=$(echo ${v#f} | tr _ ,) python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline
   done
 done
 exit 0
