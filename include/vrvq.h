@@ -406,6 +406,41 @@ int vrvq_masked_sum(const float* z_q_is, const float* mask, int batch, int nq, i
 int vrvq_bpf(const float* mask, const float* bits, int batch, int nq, int frames, float* out,
              vrvq_stream_t stream);
 
+/* Rate control from the importance map alone (codes, latents and z_q_is do not depend on the
+ * level). The frame count is the RVQ kernels' own expression, two fp32 roundings:
+ *   s = fl(fl(imp * level) * (float)nq)
+ *   n(imp, level) = s >= 0 ? (int)floorf(fminf(s, nq - 1)) + 1 : 0        (NaN gives 0)
+ * and a frame costs cum[n] bits, cum the prefix sum of bits[nq] (int32, device). All totals are
+ * int64, so they do not depend on the reduction order. 0 < nq <= 32.
+ *   vrvq_rate_curve      total_bits[b][l] = sum_t cum[n(imp[b][t], levels[l])] for imp [B][T] and
+ *                        levels [L] (device), one launch, no mask materialised
+ *   vrvq_rate_solve      per group g of rows group_off[g] .. group_off[g+1] (int32, device, G + 1
+ *                        entries; G = B rows of one is per-clip control, G = 1 over all rows one
+ *                        level for a file): the largest fp32 level in [level_lo, level_hi] whose
+ *                        total is <= budget[g] (int64, device), by bisection on the bit patterns
+ *                        of the positive floats (<= 31 halvings, exact). 0 < level_lo <=
+ *                        level_hi, both finite. Exact for imp >= 0 (the count is then monotone in
+ *                        the level); other inputs end too, with an unspecified level.
+ *                        status[g]: 0 solved; 1 infeasible (level_lo already exceeds the budget:
+ *                        level_out = level_lo, total_out its total); 2 saturated (level_hi fits,
+ *                        level_out = level_hi; also an empty group, total 0); -1 the group's range
+ *                        is not 0 <= group_off[g] <= group_off[g+1] <= B (nothing is read,
+ *                        level_out = level_lo, total_out = 0). total_out[g] is the total at
+ *                        level_out[g]. One 256-thread workgroup per group; a group of up to 4096
+ *                        elements is held in registers, a larger one is re-read per iteration.
+ *   vrvq_scale_imp_rows  out[b][t] = imp[b][t] * levels[b] (one rounding). The RVQ entry points
+ *                        given this map and level = 1.0f (an exact product) compute the
+ *                        expression above for each row's own level, bit for bit. */
+int vrvq_rate_curve(const float* imp, int batch, int frames, int nq, const int* bits,
+                    const float* levels, int n_levels, long long* total_bits,
+                    vrvq_stream_t stream);
+int vrvq_rate_solve(const float* imp, int batch, int frames, int nq, const int* bits,
+                    const int* group_off, int n_groups, const long long* budget, float level_lo,
+                    float level_hi, float* level_out, long long* total_out, int* status,
+                    vrvq_stream_t stream);
+int vrvq_scale_imp_rows(const float* imp, int batch, int frames, const float* levels, float* out,
+                        vrvq_stream_t stream);
+
 /* Variable-length code packing from importance masks (the reference's
  * DACFile, models/dac_base.py:19-58, stores the full uint16 code matrix). Packed stream is
  * clip-major, frame-major, stage-minor uint16: packed[clip_off[b] + frame_off[b,t] + i] =

@@ -61,6 +61,9 @@ SIGNATURES = {
     "vrvq_scale_imp": [_P, _I, _F, _F, _P, _P],
     "vrvq_masked_sum": [_P, _P, _I, _I, _I, _I, _P, _P],
     "vrvq_bpf": [_P, _P, _I, _I, _I, _P, _P],
+    "vrvq_rate_curve": [_P, _I, _I, _I, _P, _P, _I, _P, _P],
+    "vrvq_rate_solve": [_P, _I, _I, _I, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P],
+    "vrvq_scale_imp_rows": [_P, _I, _I, _P, _P, _P],
     "vrvq_pack_counts": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "vrvq_pack_codes": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "vrvq_unpack_offsets": [_P, _I, _I, _P, _P, _P],

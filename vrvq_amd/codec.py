@@ -188,12 +188,40 @@ def _as_signal(obj, sample_rate) -> AudioSignal:
 
 
 # ----------------------------------------------------------------------------- compress
-@torch.no_grad()
 def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
              verbose: bool = False, normalize_db: Optional[float] = -16,
              n_quantizers: Optional[int] = None, level: float = 1.0, max_batch: int = 64,
-             sample_rate: Optional[int] = None) -> DACFile:
-    """models/dac_base.py:162-240 on the HIP encode path (see the module docstring)."""
+             sample_rate: Optional[int] = None, target_kbps: Optional[float] = None) -> DACFile:
+    """models/dac_base.py:162-240 on the HIP encode path (see the module docstring).
+
+    `target_kbps` (VBR models) replaces `level`: the windows are encoded once, and one level for
+    the whole file -- the largest in the model's [level_min, level_max] at which all windows
+    together stay within target_kbps over their frames -- is solved on the device from their
+    importance maps (utils.solve_levels, pooled), so bits move between windows. Codes do not
+    depend on the level: only the masks are built from it, there is no second encode, and the
+    file equals compress(level=solve_file_level(...))."""
+    return _compress(model, audio_path_or_signal, False, win_duration, verbose, normalize_db,
+                     n_quantizers, level, max_batch, sample_rate, target_kbps)
+
+
+def solve_file_level(model, audio, target_kbps: float, **compress_kw) -> float:
+    """The level compress(model, audio, target_kbps=target_kbps, **compress_kw) encodes the file
+    at, without building the file."""
+    return _compress(model, audio, True, target_kbps=target_kbps, **compress_kw)
+
+
+@torch.no_grad()
+def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose=False,
+              normalize_db=-16, n_quantizers=None, level=1.0, max_batch=64, sample_rate=None,
+              target_kbps=None):
+    vbr = getattr(model, "model_type", "CBR") == "VBR"
+    if target_kbps is not None:
+        if not vbr:
+            raise ValueError("compress: target_kbps needs a VBR model (this one is CBR)")
+        if n_quantizers is not None:
+            raise ValueError("compress: target_kbps cannot be combined with n_quantizers")
+        if level != 1.0:
+            raise ValueError("compress: give either level or target_kbps, not both")
     sig = _as_signal(audio_path_or_signal, sample_rate or model.sample_rate)
     model.eval()
     original_padding = model.padding
@@ -232,11 +260,14 @@ def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
             x = audio[..., i:i + n_samples]
             clips.append(torch.nn.functional.pad(x, (0, n_samples - x.shape[-1])))
         clips = torch.cat(clips, 0)                          # (n_win * nb*nac, 1, n_samples)
-        codes = []
-        vbr = getattr(model, "model_type", "CBR") == "VBR"
+        codes, imps = [], []
         for c0 in range(0, clips.shape[0], max_batch):
             x = model.preprocess(clips[c0:c0 + max_batch].contiguous(), model.sample_rate)
-            if vbr and n_quantizers is None:
+            if target_kbps is not None:  # codes and imp_map do not depend on the level
+                out = model.encode(x, None, 1, want_z_q_is=False)
+                c = out["codes"]
+                imps.append(out["imp_map"])
+            elif vbr and n_quantizers is None:
                 out = model.encode(x, None, level, want_z_q_is=False)
                 c = out["codes"].masked_fill(out["mask_imp"] == 0, model.codebook_size)
             else:
@@ -247,6 +278,24 @@ def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
             if verbose:
                 print(f"[compress] windows {c0}..{c0 + x.shape[0]} of {clips.shape[0]}")
         codes = torch.cat(codes, 0)                          # (n_win * nb*nac, Nq, frames)
+        if target_kbps is not None:
+            from . import utils
+            imp = torch.cat(imps, 0)
+            nq = model.n_codebooks
+            lv, _, status = utils.solve_levels(
+                imp, target_kbps, nq=nq, sample_rate=model.sample_rate,
+                hop_length=model.hop_length, level_min=model.quantizer.level_min,
+                level_max=model.quantizer.level_max, pooled=True)
+            if int(status.item()) == 1:
+                raise ValueError(f"compress: {target_kbps} kbps is below the file's rate at "
+                                 f"level_min = {model.quantizer.level_min}")
+            file_level = float(lv.item())
+            if level_only:
+                return file_level
+            mask = utils.generate_mask_hard(utils.scale_importance(imp, file_level, float(nq)), nq)
+            codes = codes.masked_fill(mask == 0, model.codebook_size)
+        elif level_only:
+            raise ValueError("solve_file_level: target_kbps is required")
         chunk_length = codes.shape[-1]
         nw = len(starts)
         codes = codes.reshape(nw, nb * nac, codes.shape[1], chunk_length)

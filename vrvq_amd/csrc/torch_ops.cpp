@@ -673,6 +673,74 @@ Tensor bpf(const Tensor& mask, const Tensor& bits) {
   return out;
 }
 
+// --------------------------------------------------------------------------- rate control
+// Bits of every clip at every level and the level that meets a bit budget, from the importance
+// map alone (include/vrvq.h "Rate control"); what scripts/inference.py:88-112 gets from one
+// mask + bpf per level.
+int64_t imp_rows(const Tensor& imp, const char* fn) {
+  check_t(imp, "imp");
+  TORCH_CHECK(imp.dim() >= 2 && imp.numel() > 0 &&
+                  imp.numel() == imp.size(0) * imp.size(-1),
+              fn, ": imp must be (B, T) or (B, 1, T)");
+  TORCH_CHECK(imp.size(0) < (1LL << 31) && imp.size(-1) < (1LL << 31), fn, ": imp too large");
+  return imp.size(0);
+}
+
+Tensor rate_curve(const Tensor& imp, const Tensor& levels, const Tensor& bits) {
+  const int64_t B = imp_rows(imp, "rate_curve"), T = imp.size(-1);
+  check_on(levels, imp, "levels");
+  check_on(bits, imp, "bits", at::kInt);
+  TORCH_CHECK(levels.dim() == 1 && bits.dim() == 1, "rate_curve: levels (L,), bits (nq,)");
+  c10::DeviceGuard guard(imp.device());
+  const int64_t L = levels.numel();
+  Tensor total = at::empty({B, L}, imp.options().dtype(at::kLong));
+  if (L > 0)
+    check_rc(vrvq_rate_curve(imp.data_ptr<float>(), (int)B, (int)T, (int)bits.numel(),
+                             bits.data_ptr<int>(), levels.data_ptr<float>(), (int)L,
+                             reinterpret_cast<long long*>(total.data_ptr<int64_t>()),
+                             stream_of(imp)),
+             "vrvq_rate_curve");
+  return total;
+}
+
+std::tuple<Tensor, Tensor, Tensor> rate_solve(const Tensor& imp, const Tensor& bits,
+                                              const Tensor& group_off, const Tensor& budget,
+                                              double level_lo, double level_hi) {
+  const int64_t B = imp_rows(imp, "rate_solve"), T = imp.size(-1);
+  check_on(bits, imp, "bits", at::kInt);
+  check_on(group_off, imp, "group_off", at::kInt);
+  check_on(budget, imp, "budget", at::kLong);
+  TORCH_CHECK(bits.dim() == 1 && group_off.dim() == 1 && group_off.numel() >= 2,
+              "rate_solve: bits (nq,), group_off (G + 1,)");
+  const int64_t G = group_off.numel() - 1;
+  TORCH_CHECK(budget.dim() == 1 && budget.numel() == G, "rate_solve: one budget per group");
+  c10::DeviceGuard guard(imp.device());
+  Tensor level = at::empty({G}, imp.options());
+  Tensor total = at::empty({G}, imp.options().dtype(at::kLong));
+  Tensor status = at::empty({G}, imp.options().dtype(at::kInt));
+  check_rc(vrvq_rate_solve(imp.data_ptr<float>(), (int)B, (int)T, (int)bits.numel(),
+                           bits.data_ptr<int>(), group_off.data_ptr<int>(), (int)G,
+                           reinterpret_cast<const long long*>(budget.data_ptr<int64_t>()),
+                           (float)level_lo, (float)level_hi, level.data_ptr<float>(),
+                           reinterpret_cast<long long*>(total.data_ptr<int64_t>()),
+                           status.data_ptr<int>(), stream_of(imp)),
+           "vrvq_rate_solve");
+  return {level, total, status};
+}
+
+// imp_map * level[:, None] (models/quantize.py:389 with the per-item level of :378-386).
+Tensor scale_imp_rows(const Tensor& imp, const Tensor& levels) {
+  const int64_t B = imp_rows(imp, "scale_imp_rows"), T = imp.size(-1);
+  check_on(levels, imp, "levels");
+  TORCH_CHECK(levels.numel() == B, "scale_imp_rows: one level per row of imp");
+  c10::DeviceGuard guard(imp.device());
+  Tensor out = at::empty_like(imp);
+  check_rc(vrvq_scale_imp_rows(imp.data_ptr<float>(), (int)B, (int)T, levels.data_ptr<float>(),
+                               out.data_ptr<float>(), stream_of(imp)),
+           "vrvq_scale_imp_rows");
+  return out;
+}
+
 // --------------------------------------------------------------------------- code packing
 // Variable-length packing. The packed length is data-dependent, so
 // pack_codes takes it from the host (vrvq_amd/codes_io.py reads clip_off[B]).
@@ -1118,6 +1186,11 @@ TORCH_LIBRARY(vrvq, m) {
   m.def("imp_mask(Tensor s, int nq) -> Tensor");
   m.def("masked_sum(Tensor z_q_is, Tensor mask) -> Tensor");
   m.def("bpf(Tensor mask, Tensor bits) -> Tensor");
+  m.def("rate_curve(Tensor imp, Tensor levels, Tensor bits) -> Tensor");
+  m.def(
+      "rate_solve(Tensor imp, Tensor bits, Tensor group_off, Tensor budget, float level_lo, "
+      "float level_hi) -> (Tensor, Tensor, Tensor)");
+  m.def("scale_imp_rows(Tensor imp, Tensor levels) -> Tensor");
   m.def("pack_counts(Tensor mask) -> (Tensor, Tensor, Tensor)");
   m.def(
       "pack_codes(Tensor codes, Tensor counts, Tensor clip_off, int total, int ncode) "
@@ -1177,6 +1250,9 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("imp_mask", &imp_mask); \
   m.impl("masked_sum", &masked_sum); \
   m.impl("bpf", &bpf); \
+  m.impl("rate_curve", &rate_curve); \
+  m.impl("rate_solve", &rate_solve); \
+  m.impl("scale_imp_rows", &scale_imp_rows); \
   m.impl("pack_counts", &pack_counts); \
   m.impl("pack_codes", &pack_codes); \
   m.impl("unpack_offsets", &unpack_offsets); \

@@ -334,6 +334,28 @@ class ResidualVectorQuantize(nn.Module):
         return z_q, z_p, codes
 
 
+def _check_rate_args(vbr: bool, training: bool, n_quantizers, level, target_kbps,
+                     default_level) -> bool:
+    """True when the call asks for rate control: a per-clip level (a tensor of one dimension or
+    more) or target_kbps. Both need a VBR quantizer in eval mode without n_quantizers, and they
+    exclude each other; anything else raises ValueError before a kernel runs. A scalar level
+    alone is today's call and is not touched."""
+    per_clip = torch.is_tensor(level) and level.dim() > 0
+    if target_kbps is None and not per_clip:
+        return False
+    what = "target_kbps" if target_kbps is not None else "a per-clip level"
+    if target_kbps is not None and (per_clip or not (
+            level is default_level or (default_level is not None and level == default_level))):
+        raise ValueError("give either level or target_kbps, not both")
+    if not vbr:
+        raise ValueError(f"{what} needs a VBR model (this one is CBR)")
+    if n_quantizers is not None:
+        raise ValueError(f"{what} cannot be combined with n_quantizers")
+    if training:
+        raise ValueError(f"{what} is an eval-mode feature (training draws its own levels)")
+    return True
+
+
 class VBRResidualVectorQuantize(ResidualVectorQuantize):
     """Variable-bitrate RVQ with importance-map gating (models/quantize.py:288-449)."""
 
@@ -355,8 +377,17 @@ class VBRResidualVectorQuantize(ResidualVectorQuantize):
                                            detach_input=detach_imp_map_input)
 
     def forward(self, z: torch.Tensor, n_quantizers: int = None, feat_enc: torch.Tensor = None,
-                level: float = None, want_z_q_is: bool = True):
-        if n_quantizers is None and level is None:
+                level: float = None, want_z_q_is: bool = True, target_kbps=None,
+                sample_rate: int = None, hop_length: int = None):
+        """`level` may be a (B,) float32 tensor, one level per clip (eval only): each row of the
+        importance map is scaled by its own level and the RVQ runs at level 1.0, which gives the
+        scalar-level expression for that row bit for bit. `target_kbps` (a number or one per
+        clip) solves each clip's level within [level_min, level_max] on the device
+        (utils.solve_levels) and adds "level", "bpf" and "rate_status" (B,) to the dict; it needs
+        the codec's sample_rate and hop_length (DAC_VRVQ.encode passes them)."""
+        rate_control = _check_rate_args(True, self.training, n_quantizers, level, target_kbps,
+                                        default_level=None)
+        if n_quantizers is None and level is None and target_kbps is None:
             raise AssertionError("level must be specified in VBR mode")
         if self.training:
             if n_quantizers is not None:  # CBR mode: ones + dropout / full rows (:397-414)
@@ -366,8 +397,6 @@ class VBRResidualVectorQuantize(ResidualVectorQuantize):
         B, D, T = z.shape
         nq = self.n_codebooks
         if n_quantizers is None:
-            if level is None:
-                raise AssertionError("level must be specified in VBR mode")
             mode = "VBR"
         else:
             mode = "CBR"
@@ -382,9 +411,27 @@ class VBRResidualVectorQuantize(ResidualVectorQuantize):
         st = self.stacked()
         if mode == "VBR":
             imp_map = self.imp_subnet(feat_enc.contiguous())                 # (B, 1, T)
-            imp, lvl = imp_map.reshape(B, T), float(level)
+            imp = imp_map.reshape(B, T)
+            rate = {}
+            if rate_control:
+                if target_kbps is not None:
+                    if sample_rate is None or hop_length is None:
+                        raise ValueError("target_kbps needs sample_rate and hop_length")
+                    from . import utils
+                    levels, bpf, status = utils.solve_levels(
+                        imp, target_kbps, nq=nq, sample_rate=sample_rate, hop_length=hop_length,
+                        level_min=self.level_min, level_max=self.level_max)
+                    rate = {"level": levels, "bpf": bpf, "rate_status": status}
+                else:
+                    if level.shape != (B,) or level.dtype != torch.float32:
+                        raise ValueError(f"a tensor level must be ({B},) float32, one per clip")
+                    levels = level.to(imp.device).contiguous()
+                # the row's own level here, level 1.0 (an exact product) in the RVQ launch
+                imp, lvl = ops.scale_imp_rows(imp, levels), 1.0
+            else:
+                lvl = float(level)
         else:
-            imp_map, imp, lvl = None, None, 1.0
+            imp_map, imp, lvl, rate = None, None, 1.0, {}
         # residual chain, z_q_is stream, importance mask, masked z_q
         codes, latents, loss_pf, z_q_is, z_q, mask = _rvq_encode(
             z, st, imp=imp, level=lvl, want_z_q_is=want_z_q_is)
@@ -398,6 +445,7 @@ class VBRResidualVectorQuantize(ResidualVectorQuantize):
             "codebook_loss": loss.clone(),
             "imp_map": imp_map,
             "mask_imp": mask,
+            **rate,  # target_kbps only: "level", "bpf", "rate_status"
         }
 
     def from_codes(self, codes: torch.Tensor, return_z_q_is=False, mask_imp=None):
@@ -553,12 +601,20 @@ class DAC_VRVQ(nn.Module, CodecMixin):
         return nn.functional.pad(audio_data, (0, right_pad))
 
     def encode(self, audio_data: torch.Tensor, n_quantizers: int = None, level: int = 1,
-               want_z_q_is: bool = True):
+               want_z_q_is: bool = True, target_kbps=None):
         """models/dac_vrvq.py:176-213. Returns the quantizer's output dict.
 
         `want_z_q_is=False` skips materialising the (B, Nq, D, T) per-codebook tensor when the
         caller does not need it (it is ~90 % of the quantizer's HBM traffic); the default keeps
-        the reference's dict."""
+        the reference's dict.
+
+        Rate control (VBR model, eval mode, no n_quantizers): `level` may be a (B,) float32
+        tensor, one level per clip, and `target_kbps` (a number or one per clip) has each clip's
+        level solved on the device within [level_min, level_max]; the dict then also holds
+        "level", "bpf" and "rate_status" (VBRResidualVectorQuantize.forward). Neither makes a
+        host sync, so both run under graph capture."""
+        rate_control = _check_rate_args(self.model_type == "VBR", self.training, n_quantizers,
+                                        level, target_kbps, default_level=1)
         ev = not self.training and not self.encoder.valid
         # the projection epilogue computes the stages the quantizer runs: all of them, or a CBR
         # prefix (n_quantizers < Nq; a VBR model raises for one in its quantizer)
@@ -573,6 +629,10 @@ class DAC_VRVQ(nn.Module, CodecMixin):
             z, feat = self.encoder(audio_data.contiguous(), return_feat=True)
         if self.model_type == "CBR":
             return self.quantizer(z, n_quantizers)
+        if rate_control:
+            return self.quantizer(z, None, feat, None if target_kbps is not None else level,
+                                  want_z_q_is=want_z_q_is, target_kbps=target_kbps,
+                                  sample_rate=self.sample_rate, hop_length=self.hop_length)
         return self.quantizer(z, n_quantizers, feat, level, want_z_q_is=want_z_q_is)
 
     def decode(self, z: torch.Tensor):
@@ -580,14 +640,21 @@ class DAC_VRVQ(nn.Module, CodecMixin):
         return self.decoder(z.contiguous())
 
     def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: int = None,
-                level: int = 1):
-        """models/dac_vrvq.py:222-252."""
+                level: int = 1, target_kbps=None):
+        """models/dac_vrvq.py:222-252. `level` as a (B,) tensor and `target_kbps` as in encode;
+        with target_kbps the dict also holds "level", "bpf" and "rate_status"."""
+        rate_control = _check_rate_args(self.model_type == "VBR", self.training, n_quantizers,
+                                        level, target_kbps, default_level=1)
         length = audio_data.shape[-1]
         audio_data = self.preprocess(audio_data, sample_rate)
-        out = self.encode(audio_data, n_quantizers, level) if self.model_type == "VBR" \
-            else self.encode(audio_data, n_quantizers)
+        if rate_control:
+            out = self.encode(audio_data, n_quantizers, level, target_kbps=target_kbps)
+        else:
+            out = self.encode(audio_data, n_quantizers, level) if self.model_type == "VBR" \
+                else self.encode(audio_data, n_quantizers)
         z_q = out["z_q"]
         x = self.decode(z_q)
+        rate = {k: out[k] for k in ("level", "bpf", "rate_status") if k in out}
         return {
             "audio": x[..., :length],
             "z": z_q,
@@ -597,4 +664,5 @@ class DAC_VRVQ(nn.Module, CodecMixin):
             "vq/codebook_loss": out["codebook_loss"],
             "imp_map": out.get("imp_map", None),
             "mask_imp": out.get("mask_imp", None),
+            **rate,
         }

@@ -291,6 +291,26 @@ def bpf(mask: torch.Tensor, bits: torch.Tensor) -> torch.Tensor:
     return _ops().bpf(mask, bits)
 
 
+def rate_curve(imp: torch.Tensor, levels: torch.Tensor, bits: torch.Tensor) -> torch.Tensor:
+    """Total bits (B, L) int64 of every row of imp (B, T) / (B, 1, T) at every level (L,), for the
+    int32 bits-per-codebook table bits (nq,) (include/vrvq.h vrvq_rate_curve)."""
+    return _ops().rate_curve(imp, levels, bits)
+
+
+def rate_solve(imp: torch.Tensor, bits: torch.Tensor, group_off: torch.Tensor,
+               budget: torch.Tensor, level_lo: float, level_hi: float):
+    """Per group of rows group_off[g]..group_off[g+1] (int32, (G + 1,)): the largest fp32 level in
+    [level_lo, level_hi] whose total bits are <= budget[g] (int64). Returns (level (G,) float32,
+    total (G,) int64, status (G,) int32: 0 solved, 1 infeasible, 2 saturated, -1 bad range); no
+    host sync (include/vrvq.h vrvq_rate_solve)."""
+    return _ops().rate_solve(imp, bits, group_off, budget, float(level_lo), float(level_hi))
+
+
+def scale_imp_rows(imp: torch.Tensor, levels: torch.Tensor) -> torch.Tensor:
+    """imp[b] * levels[b]: one fp32 rounding per element."""
+    return _ops().scale_imp_rows(imp, levels)
+
+
 # ----------------------------------------------------------------------------- training step
 # Backward operators of the generator (include/vrvq.h "Training step"; vrvq_amd/train.py).
 def conv1d_wgrad(a, x, k: int, stride: int = 1, pad: int = 0, dil: int = 1,
@@ -491,6 +511,20 @@ def _register_fakes():
     @reg("vrvq::bpf")
     def _(mask, bits):
         return f32(mask, ())
+
+    @reg("vrvq::rate_curve")
+    def _(imp, levels, bits):
+        return imp.new_empty((imp.shape[0], levels.shape[0]), dtype=torch.int64)
+
+    @reg("vrvq::rate_solve")
+    def _(imp, bits, group_off, budget, level_lo, level_hi):
+        G = group_off.shape[0] - 1
+        return (f32(imp, (G,)), imp.new_empty((G,), dtype=torch.int64),
+                imp.new_empty((G,), dtype=torch.int32))
+
+    @reg("vrvq::scale_imp_rows")
+    def _(imp, levels):
+        return torch.empty_like(imp)
 
     @reg("vrvq::pack_counts")
     def _(mask):

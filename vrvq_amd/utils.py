@@ -5,6 +5,7 @@ from __future__ import annotations
 import math
 from typing import Sequence
 
+import numpy as np
 import torch
 
 from . import ops
@@ -51,6 +52,86 @@ def cal_bpf_tensor(mask: torch.Tensor, bits_per_codebook: Sequence[float]) -> to
     """Same as cal_bpf_from_mask but returns a 0-d device tensor (no host sync)."""
     bits = torch.as_tensor(list(bits_per_codebook), dtype=torch.float32).to(mask.device)
     return ops.bpf(mask.contiguous(), bits)
+
+
+def _device_const(values, dtype, device) -> torch.Tensor:
+    """A small 1-d device tensor of Python numbers. Equal values are one fill; under stream
+    capture (where a host-to-device copy of pageable memory is not allowed) unequal ones are one
+    fill each."""
+    values = list(values)
+    if all(v == values[0] for v in values):
+        return torch.full((len(values),), values[0], dtype=dtype, device=device)
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        return torch.cat([torch.full((1,), v, dtype=dtype, device=device) for v in values])
+    return torch.tensor(values, dtype=dtype, device=device)
+
+
+def _bits_table(bits_per_codebook, nq: int, device) -> torch.Tensor:
+    if isinstance(bits_per_codebook, (int, float)):
+        bits_per_codebook = [bits_per_codebook] * nq
+    bits = [int(b) for b in bits_per_codebook]
+    if len(bits) != nq or any(b != v for b, v in zip(bits, bits_per_codebook)):
+        raise ValueError(f"bits_per_codebook: {nq} integer bit counts expected")
+    return _device_const(bits, torch.int32, device)
+
+
+def _imp_rows(imp_map: torch.Tensor) -> torch.Tensor:
+    imp = _as_scaled(imp_map)
+    if imp.dim() < 2 or imp.numel() != imp.shape[0] * imp.shape[-1]:
+        raise RuntimeError("importance map must be (B, T) or (B, 1, T)")
+    return imp.reshape(imp.shape[0], imp.shape[-1])
+
+
+def rate_curve(imp_map: torch.Tensor, levels, nq: int, bits_per_codebook=10) -> torch.Tensor:
+    """Bits per frame of every clip at every level, (B, L) float32, in one launch and without
+    building a mask: the frame count of the RVQ kernels (include/vrvq.h "Rate control") summed
+    per clip as integers, divided by T."""
+    imp = _imp_rows(imp_map)
+    if torch.is_tensor(levels):
+        lv = levels.to(imp.device, torch.float32).reshape(-1).contiguous()
+    else:
+        lv = _device_const([float(v) for v in levels], torch.float32, imp.device)
+    total = ops.rate_curve(imp, lv, _bits_table(bits_per_codebook, nq, imp.device))
+    return (total.to(torch.float64) / imp.shape[1]).to(torch.float32)
+
+
+def kbps_to_budget(kbps: float, frames: int, sample_rate: int, hop_length: int) -> int:
+    """Whole bits that `frames` frames may take at `kbps`, at the frame rate
+    floor(sample_rate / hop_length) of scripts/inference.py:112."""
+    return int(math.floor(float(kbps) * 1000 / math.floor(sample_rate / hop_length) * frames))
+
+
+def solve_levels(imp_map: torch.Tensor, target_kbps, *, nq: int, sample_rate: int,
+                 hop_length: int, level_min: float, level_max: float, bits_per_codebook=10,
+                 pooled: bool = False):
+    """The largest level in [level_min, level_max] at which each clip (or, pooled, the whole
+    batch as one group) stays within `target_kbps`, solved on the device in one launch
+    (include/vrvq.h vrvq_rate_solve). target_kbps: a number, or one per clip (not pooled).
+    Returns device tensors (levels (G,) float32, bpf (G,) float32, status (G,) int32; 0 solved,
+    1 infeasible even at level_min, 2 level_max fits), G = B, or 1 when pooled. No host sync for
+    a number or a host sequence."""
+    imp = _imp_rows(imp_map)
+    B, T = imp.shape
+    if level_min is None or level_max is None:
+        raise ValueError("solve_levels: level_min and level_max are required")
+    if torch.is_tensor(target_kbps) or isinstance(target_kbps, np.ndarray):
+        target_kbps = target_kbps.tolist()
+    scalar = not isinstance(target_kbps, (list, tuple))
+    if pooled:
+        if not scalar:
+            raise ValueError("solve_levels: a pooled solve takes one target_kbps")
+        budgets, frames = [kbps_to_budget(target_kbps, B * T, sample_rate, hop_length)], B * T
+        off = _device_const([0, B], torch.int32, imp.device)
+    else:
+        ks = [target_kbps] * B if scalar else list(target_kbps)
+        if len(ks) != B:
+            raise ValueError(f"solve_levels: {len(ks)} targets for {B} clips")
+        budgets, frames = [kbps_to_budget(k, T, sample_rate, hop_length) for k in ks], T
+        off = torch.arange(B + 1, dtype=torch.int32, device=imp.device)
+    budget = _device_const(budgets, torch.int64, imp.device)
+    levels, total, status = ops.rate_solve(imp, _bits_table(bits_per_codebook, nq, imp.device),
+                                           off, budget, level_min, level_max)
+    return levels, (total.to(torch.float64) / frames).to(torch.float32), status
 
 
 def masked_sum(z_q_is: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
