@@ -154,6 +154,13 @@ int vrvq_conv1d_proj(const float* x, int batch, int cin, int tin, const float* a
                      const uint16_t* w3in, int nq, float* part, void* workspace,
                      long long ws_bytes, vrvq_stream_t stream);
 
+/* Debug query (host only, no launch): tile and path of the last conv launch on the MFMA tiles
+ * (vrvq_conv1d / _ws / _proj, vrvq_conv_transpose1d*), process-wide: out = {BM, BN, KS (the
+ * GEMM's taps: 2 for the phase-split view), x3 (0: fp32-input loop, 1: x3 on plain K chunks,
+ * 2: x3 on pair chunks), S (split-K parts, 0: unsplit)}; all 0 before the first such launch.
+ * The tests use it to assert the tile they claim to pin. */
+int vrvq_conv_last_launch(int out[5]);
+
 /* Pack a folded Conv1d weight w[Cout][Cin][k] into [Cin][k][cout_pad]. */
 int vrvq_pack_conv1d_weight(const float* w, int cout, int cin, int k, int cout_pad,
                             float* w_packed, vrvq_stream_t stream);

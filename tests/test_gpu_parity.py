@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import vrvq_amd
+import rvq_ref as R
 from conftest import load_golden, rel_err
 from oracle.vrvq_oracle import Oracle
 from vrvq_amd import ops
@@ -668,6 +669,11 @@ def _rvq_fp64_reference(z, st, imp, level):
 
 
 def _random_rvq(nq, ncode, seed):
+    """Unit-scale biases and codebooks, every 3-dim parameter (weight_g, weight_v) at 0.05: the
+    folded in_proj rows have norm ~0.04, so z_e is the bias for every frame and each stage picks
+    1 to 3 distinct codes (tests/test_rvq_inputs.py test_old_recipe_is_near_constant). Good for
+    launch structure and bit-identity between paths, NOT for the argmin: the tests that judge the
+    distance scan draw from tests/rvq_ref.py diverse_rvq_params instead."""
     gen = torch.Generator().manual_seed(seed)
     q = vrvq_amd.model.ResidualVectorQuantize(input_dim=1024, n_codebooks=nq, codebook_size=ncode,
                                               codebook_dim=8)
@@ -707,6 +713,114 @@ def test_rvq_encode_vs_fp64(nq, ncode, B, T, vbr):
     assert rel_err(loss.cpu().numpy(), ref_loss.cpu().numpy()) < 1e-4
     # the masked sum of the op's own z_q_is, in stage order, is its z_q bit for bit
     assert torch.equal(vrvq_amd.masked_sum(zqis, mask), zq)
+
+
+def load_rvq(params):
+    """A ResidualVectorQuantize on the device holding rvq_ref.Params (stacked per-stage tensors)."""
+    nq, N, d = params.cb.shape
+    D = params.v_in.shape[1]
+    q = vrvq_amd.model.ResidualVectorQuantize(input_dim=D, n_codebooks=nq, codebook_size=N,
+                                              codebook_dim=d)
+    with torch.no_grad():
+        for i, s in enumerate(q.quantizers):
+            s.in_proj.weight_g.copy_(params.g_in[i * d:(i + 1) * d].reshape(d, 1, 1))
+            s.in_proj.weight_v.copy_(params.v_in[i * d:(i + 1) * d].reshape(d, D, 1))
+            s.in_proj.bias.copy_(params.b_in[i])
+            s.out_proj.weight_g.copy_(params.g_out[i * D:(i + 1) * D].reshape(D, 1, 1))
+            s.out_proj.weight_v.copy_(params.v_out[i * D:(i + 1) * D].reshape(D, d, 1))
+            s.out_proj.bias.copy_(params.b_out[i])
+            s.codebook.weight.copy_(params.cb[i])
+    return q.to(DEV).eval()
+
+
+_NAMES = ("codes", "latents", "loss_pf", "z_q_is", "z_q", "mask")
+
+
+def rvq_three_entries(z, st, imp, level):
+    """The quantizer's three eval entry points on the same inputs: rvq_encode as three launches,
+    rvq_encode as the fused launch, and rvq_project's partials -> rvq_encode_part (the default
+    encode's rvq_pt_kernel). Asserts all six outputs bit-equal and returns them."""
+    from test_gpu_rvq_part import _part_call, _project
+    from vrvq_amd import _lib
+    outs = []
+    # forget the code a timeout test may have left in this stream's word (only this read clears it)
+    _lib.rvq_sync_error(torch.cuda.current_stream().cuda_stream)
+    prev = _lib.rvq_path(0)
+    try:
+        for path in (1, 2):
+            _lib.rvq_path(path)
+            outs.append(ops.rvq_encode(z, *st.codes_args(), imp=imp, level=level))
+            torch.cuda.synchronize()
+    finally:
+        _lib.rvq_path(prev)
+    outs.append(_part_call(_project(z, st), z.shape[2], st, imp, level))
+    torch.cuda.synchronize()
+    assert _lib.rvq_sync_error(torch.cuda.current_stream().cuda_stream) == 0
+    for o, entry in zip(outs[1:], ("fused", "part")):
+        for name, x, y in zip(_NAMES, outs[0], o):
+            assert torch.equal(x, y), (entry, name)
+    return outs[0]
+
+
+def check_rvq_vs_fp64(out, z, params, imp, level, label):
+    """Codes under rvq_ref.check_codes (every decision judged on the fp64 chain teacher-forced
+    on the GPU's codes), mask exact, z_q_is / z_q / latents within 1e-5 of that chain, and the
+    masked sum of the op's own z_q_is its z_q bit for bit. Prints the figures."""
+    codes, lat, _loss, zqis, zq, mask = out
+    nq, B, T = codes.shape[1], codes.shape[0], codes.shape[2]
+    res = R.check_codes(codes, z, params)
+    ref = res["ref"]
+    print(f"{label}: eps_d={res['eps_d']:.2e} margin={res['margin']:.2e} "
+          f"worst={res['worst']:.2e} mismatch={res['share']:.4%} "
+          f"min distinct={min(R.distinct_per_stage(codes))}")
+    rmask = R.mask_fp64(imp, level, nq, B, T)
+    np.testing.assert_array_equal(mask.cpu().numpy(), rmask.numpy())
+    assert rel_err(zqis.cpu().numpy(), ref.z_q_is.numpy()) < 1e-5
+    assert rel_err(zq.cpu().numpy(), (ref.z_q_is * rmask[:, :, None, :]).sum(1).numpy()) < 1e-5
+    assert rel_err(lat.cpu().numpy(), ref.latents.numpy()) < 1e-5
+    assert torch.equal(vrvq_amd.masked_sum(zqis, mask), zq)
+    return res
+
+
+@pytest.mark.parametrize("nq,ncode,B,T,vbr", R.DIVERSE_SHAPES)
+def test_rvq_diverse_vs_fp64(nq, ncode, B, T, vbr):
+    """The argmin on inputs that exercise it (tests/rvq_ref.py: 100+ distinct codes per stage,
+    every 256-code quarter of the codebook): the three launches, the fused launch and the default
+    rvq_pt_kernel agree bit for bit, and EVERY decision is within 8 eps_d of its stage's fp64
+    minimum with <= 0.5 % differing from the fp64 argmin (check_codes)."""
+    params, z, imp = R.diverse_case(nq, ncode, B, T, vbr)
+    st = load_rvq(params).stacked()
+    zd = z.to(DEV)
+    impd = None if imp is None else imp.to(DEV)
+    out = rvq_three_entries(zd, st, impd, 0.75)
+    R.assert_diverse(out[0], ncode)
+    check_rvq_vs_fp64(out, z, params, imp, 0.75, f"diverse {(nq, ncode, B, T)}")
+
+
+TIE_CASES = [(p, nq, n) for p in ("half", "pair", "mirror")
+             for nq, n in ((8, 1024), (4, 512), (4, 768), (4, 256)) if (p, n) != ("mirror", 768)]
+
+
+@pytest.mark.parametrize("pattern,nq,ncode", TIE_CASES)
+def test_rvq_exact_ties_take_lowest_index(pattern, nq, ncode):
+    """Every codebook row duplicated at a second index (rvq_ref.tie_codebook), so every decision
+    at every stage is an exact tie of two identical rows: all three entry points and rvq_nearest
+    (from_latents) return the LOWER index of the pair -- README / DESIGN's lowest-index argmin --
+    and the codes pass check_codes. Strict: it assumes identical rows get bit-identical distances
+    (the same codebook_prep row, the same 8-term dot), whatever their position."""
+    params, gen = R.diverse_rvq_params(nq, ncode, 900 + nq + ncode)
+    params = params._replace(cb=R.tie_codebook(params.cb, pattern))
+    z = R.diverse_z(2, 87, gen)
+    st = load_rvq(params).stacked()
+    out = rvq_three_entries(z.to(DEV), st, None, 1.0)
+    codes = out[0].cpu()
+    res = check_rvq_vs_fp64(out, z, params, None, 1.0, f"ties {pattern} {(nq, ncode)}")
+    near = ops.rvq_nearest(out[1], st.cbn, st.c2, nq).cpu()
+    R.judge(near, res["ref"].dist, res["margin"], 0.005)
+    for name, c in (("chain", codes), ("nearest", near)):
+        high = ~R.lower_twin(c, ncode, pattern)
+        assert not bool(high.any()), (f"{name}: {int(high.sum())} of {c.numel()} decisions took "
+                                      f"the higher twin, first at {high.nonzero()[0].tolist()}")
 
 
 @pytest.mark.parametrize("nq,B,T", [(8, 32, 87), (32, 64, 87), (28, 3, 70), (1, 4, 87), (5, 3, 40),

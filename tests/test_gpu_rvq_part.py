@@ -14,9 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+import rvq_ref as R
 import vrvq_amd
 from conftest import rel_err
-from test_gpu_parity import _random_rvq, _rvq_fp64_reference
+from test_gpu_parity import _random_rvq, _rvq_fp64_reference, check_rvq_vs_fp64, load_rvq
 from vrvq_amd import _lib, ops
 
 pytestmark = pytest.mark.gpu
@@ -67,9 +68,11 @@ def _equal(a, b):
     (2, 1024, 1, 8, 3, 1), (3, 1024, 40, 1, 3, 1), (2, 1024, 97, 28, 3, 1), (2, 512, 130, 8, 7, 3),
     (48, 1024, 87, 8, 3, 1)])
 def test_conv1d_proj_partials_are_project_bits(B, cin, T, nq, k, pad):
-    """The epilogue's partials equal vrvq_rvq_project's on the conv's own z bit for bit (every
-    tile width: 32-wide at T = 87, 96-wide at B = 48, 128-wide at T = 862 / 130; one frame; odd
-    nq; nq = 1 / 28 / 32), and want_z returns z exactly as the plain conv writes it."""
+    """The epilogue's partials equal vrvq_rvq_project's on the conv's own z bit for bit (the
+    split-K epilogue launch on 96-wide tiles at every T <= 96 case of these deep layers, unsplit
+    128-wide tiles at T = 862 / 97 and 64-wide at T = 130; test_conv1d_proj_unsplit_tiles pins the
+    unsplit 32- / 96-wide tiles; one frame; odd nq; nq = 1 / 28 / 32), and want_z returns z
+    exactly as the plain conv writes it."""
     conv, snake, gen = _conv(cin, k, pad, 7 * B + T + nq)
     q, _ = _random_rvq(nq, 1024, 11 * nq + T)
     st = q.stacked()
@@ -322,3 +325,187 @@ def test_encode_cbr_prefix_projected_matches_channel_major():
             torch.cuda.synchronize()
             for key in a:
                 assert (a[key] is None and b[key] is None) or torch.equal(a[key], b[key]), (n, key)
+
+
+# ------------------------------------------------------------------ diverse codes (tests/rvq_ref.py)
+def _capacity0(part, T, st, imp, level):
+    prev = _lib.rvq_debug_capacity(0)
+    try:
+        return _part_call(part, T, st, imp, level)
+    finally:
+        _lib.rvq_debug_capacity(prev)
+
+
+def _diverse_device_case(nq, ncode, B, T):
+    params, z, imp = R.diverse_case(nq, ncode, B, T)
+    st = load_rvq(params).stacked()
+    return params, z, imp, st, z.to(DEV), imp.to(DEV)
+
+
+@pytest.mark.parametrize("nq,ncode,B,T", [
+    (8, 1024, 32, 87), (32, 1024, 64, 87),   # the configs[1] / configs[2] grids
+    (28, 1024, 40, 87),                      # ragged
+    (8, 1024, 2, 97), (8, 1024, 1, 862), (4, 768, 2, 12), (8, 1024, 2, 3)])
+def test_rvq_part_diverse_paths_bit_identical(nq, ncode, B, T):
+    """On inputs that exercise the argmin (100+ distinct codes per stage): rvq_pt_kernel, the
+    three launches and the capacity-0 two-launch fallback return all six outputs bit for bit,
+    and the first clips' codes pass check_codes (every decision within 8 eps_d of its stage's
+    fp64 minimum, <= 0.5 % off the fp64 argmin)."""
+    params, z, imp, st, zd, impd = _diverse_device_case(nq, ncode, B, T)
+    # forget the code a timeout test may have left in this stream's word (check_errors() reads
+    # the process's host word and leaves the stream's; only this read clears it)
+    _lib.rvq_sync_error(torch.cuda.current_stream().cuda_stream)
+    part = _project(zd, st)
+    want = _three_launches(zd, st, impd, 0.75)
+    got = _part_call(part, T, st, impd, 0.75)
+    fb = _capacity0(part, T, st, impd, 0.75)
+    torch.cuda.synchronize()
+    _equal(got, want)
+    _equal(fb, want)
+    assert _lib.rvq_sync_error(torch.cuda.current_stream().cuda_stream) == 0
+    if B * T >= 80:
+        R.assert_diverse(got[0], ncode)
+    n = min(B, 4)
+    check_rvq_vs_fp64([None if o is None else o[:n] for o in got], z[:n], params, imp[:n], 0.75,
+                      f"part diverse {(nq, ncode, B, T)}")
+
+
+def test_rvq_part_diverse_graph_replay_and_streams():
+    """test_rvq_part_graph_replay_and_streams on diverse inputs: a captured graph's replays and
+    eager calls on two streams under a GEMM side load give the three launches' bits."""
+    params, z, imp, st, zd, impd = _diverse_device_case(8, 1024, 32, 87)
+    part = _project(zd, st)
+    want = _three_launches(zd, st, impd, 1.0)
+    R.assert_diverse(want[0], 1024)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        _part_call(part, 87, st, impd, 1.0)
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        out = _part_call(part, 87, st, impd, 1.0)
+    g.replay()
+    torch.cuda.synchronize()
+    _equal(out, want)
+    s1, s2, side = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
+    a = torch.randn(2048, 2048, device=DEV)
+    outs = []
+    for r in range(4):
+        st_ = s1 if r % 2 == 0 else s2
+        st_.wait_stream(torch.cuda.current_stream())
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(r + 1):
+                a = (a @ a) * (1.0 / 2048)
+        with torch.cuda.stream(st_):
+            outs.append(_part_call(part, 87, st, impd, 1.0))
+    torch.cuda.synchronize()
+    for o in outs:
+        _equal(o, want)
+
+
+@pytest.mark.parametrize("name", ["golden_rvq_stress_nq8", "golden_rvq_stress_nq32"])
+def test_rvq_stress_fixtures_on_default_path(manifest, name):
+    """The reference's stress fixtures (57-178 distinct codes per stage) through the DEFAULT
+    encode's quantizer entry, rvq_project's partials -> rvq_encode_part, as rvq_pt_kernel and as
+    the capacity-0 fallback, with the fixture's own importance map at level 1: codes and mask
+    exactly the reference's, z_q within TOL."""
+    from conftest import load_golden
+    from test_gpu_parity import TOL, model_for, t
+    g = load_golden(name)
+    st = model_for(manifest, name).quantizer.stacked()
+    z = t(g["z"])
+    B, _, T = z.shape
+    imp = t(g["imp_map"]).reshape(B, T).contiguous()
+    _lib.rvq_sync_error(torch.cuda.current_stream().cuda_stream)  # forget an earlier test's code
+    part = _project(z, st)
+    for run in (_part_call, _capacity0):
+        codes, _lat, _loss, _zqis, zq, mask = run(part, T, st, imp, 1.0)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(codes.cpu().numpy(), g["codes"])
+        np.testing.assert_array_equal(mask.cpu().numpy(), g["mask_imp"])
+        assert rel_err(zq.cpu().numpy(), g["z_q"]) < TOL
+    assert _lib.rvq_sync_error(torch.cuda.current_stream().cuda_stream) == 0
+
+
+# ------------------------------------------------------------------ projection epilogue, every tile
+# name, cin, B, T, mode, the launch {BM, BN, KS, x3, S} (conv.hip dispatch_tiles: T <= 96 runs
+# 32-wide tiles, 96-wide from 384 workgroups = B 48; T = 130 64-wide, T = 97 128-wide; k3 runs
+# plain x3 chunks; Cin = 128 has too few K chunks to split, the deep layer splits in 4 when it
+# has a workspace). mode: "op" the torch op (always offers the workspace), "nows" the C-ABI with
+# workspace = NULL, "fp32" the fp32-input loop (no w_x3).
+PROJ_TILE_CASES = [
+    ("x3-32", 128, 3, 87, "op", (128, 32, 3, 1, 0)),
+    ("x3-96", 128, 48, 87, "op", (128, 96, 3, 1, 0)),
+    ("x3-64", 128, 2, 130, "op", (128, 64, 3, 1, 0)),
+    ("x3-128", 128, 2, 97, "op", (128, 128, 3, 1, 0)),
+    ("deep-nows-32", 1024, 3, 87, "nows", (128, 32, 3, 1, 0)),
+    ("deep-nows-96", 1024, 48, 87, "nows", (128, 96, 3, 1, 0)),
+    ("fp32-32", 128, 3, 87, "fp32", (128, 32, 3, 0, 0)),
+    ("fp32-96", 128, 48, 87, "fp32", (128, 96, 3, 0, 0)),
+    ("fp32-64", 128, 2, 130, "fp32", (128, 64, 3, 0, 0)),
+    ("splitk", 1024, 3, 87, "op", (128, 96, 3, 1, 4)),   # the control: the default deep layer
+]
+
+
+def _launch():
+    d = _lib.conv_last_launch()
+    return tuple(d[k] for k in ("BM", "BN", "KS", "x3", "S"))
+
+
+@pytest.mark.parametrize("nq", [1, 9, 32])
+@pytest.mark.parametrize("case", PROJ_TILE_CASES, ids=lambda c: c[0])
+def test_conv1d_proj_unsplit_tiles(case, nq):
+    """proj_epilogue on every tile that reaches it: the unsplit x3 tiles of every
+    width, the deep layer without a workspace, the fp32-input loop, and the split-K epilogue
+    launch as the control. vrvq_conv_last_launch names the tile the case claims; the partials
+    are vrvq_rvq_project's bits on the launch's own z; z is the plain conv's on the same path
+    bit for bit; and each partial is within (128 + 4) 2^-24 sum_c |W_in| |z| of the fp64 sum over
+    its 128-channel split (128 fp32 accumulations, the three dropped bf16 cross products
+    <= 3 2^-24, one rounding). nq = 9 (72 rows) leaves a half-valid last row tile."""
+    _name, cin, B, T, mode, launch = case
+    conv, snake, gen = _conv(cin, 3, 1, 7 * B + T + nq)
+    st = load_rvq(R.diverse_rvq_params(nq, 1024, 11 * nq + T)[0]).stacked()
+    x = torch.randn(B, cin, T, generator=gen).to(DEV)
+    wp, cout_pad = conv.prepared()
+    alpha, inv = snake.prepared()
+    bias = conv.bias.detach()
+    need = ctypes.c_longlong(-1)
+    _lib.call("vrvq_conv1d_workspace", B, cin, T, 1024, 3, 1, 1, 1, 0 if mode == "fp32" else 1,
+              ctypes.byref(need))
+    assert (need.value > 0) == (cin == 1024 and mode != "fp32")
+    if mode == "op":
+        assert (need.value > 0) == (launch[4] > 0)
+        part, zz = conv.forward_proj(x, st.w3in(), nq, snake=snake, want_z=True)
+        got = _launch()
+        z = conv(x, snake=snake)
+    elif mode == "fp32":
+        part, zz = ops.conv1d_proj(x, wp, 1024, 3, st.w3in(), nq, 1, 1, bias=bias, alpha=alpha,
+                                   inv_alpha=inv, w_x3=None, want_z=True)
+        got = _launch()
+        z = ops.conv1d(x, wp, 1024, cout_pad, 3, 1, 1, 1, bias=bias, alpha=alpha, inv_alpha=inv,
+                       w_x3=None)
+    else:
+        w3, w3in = conv.prepared_x3(), st.w3in()
+        part = torch.empty(8, B * T, nq * 8, device=DEV)
+        zz, z = torch.empty(B, 1024, T, device=DEV), torch.empty(B, 1024, T, device=DEV)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.call("vrvq_conv1d_proj", P(x), B, cin, T, P(alpha), P(inv), P(wp), P(w3), 1024,
+                  cout_pad, 3, 1, 1, P(bias), P(zz), T, P(w3in), nq, P(part), None, 0, stream)
+        got = _launch()
+        _lib.call("vrvq_conv1d", P(x), B, cin, T, P(alpha), P(inv), P(wp), P(w3), 1024, cout_pad,
+                  3, 1, 1, 1, P(bias), None, 0, P(z), T, None, None, None, stream)
+    assert _launch() == got == launch          # the plain conv takes the same tile and path
+    torch.cuda.synchronize()
+    assert torch.equal(zz, z)
+    assert torch.equal(part, _project(zz, st))
+    # fp64 sums over each 128-channel split of the launch's z, and their absolute-value bound
+    zs = zz.double().permute(0, 2, 1).reshape(B * T, 8, 128)
+    w = st.w_in_t.double().reshape(nq, 8, 128, 8)
+    ref = torch.einsum("fsc,isck->sfik", zs, w).reshape(8, B * T, nq * 8)
+    bound = torch.einsum("fsc,isck->sfik", zs.abs(), w.abs()).reshape(8, B * T, nq * 8)
+    excess = ((part.double() - ref).abs() - 132 * 2.0 ** -24 * bound).max()
+    print(f"{_name} nq={nq}: launch={got} worst |part - fp64| / bound = "
+          f"{float(((part.double() - ref).abs() / bound).max()) / 2.0 ** -24:.2f} x 2^-24")
+    assert float(excess) <= 0.0

@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import rvq_ref as R
 import vrvq_amd
 from conftest import load_golden, rel_err
 from vrvq_amd import ops, train
@@ -291,6 +292,8 @@ def test_rvq_backward_vs_torch64(nq, B, T):
     mask[:, 0] = 1.0
     leaves = [a.to(DEV).requires_grad_() for a in (z, mask, g_in, v_in, b_in, g_out, v_out, b_out, cb)]
     z_q, commit, cbl, codes, lat = train._RvqTrain.apply(*leaves)
+    # the forward's own argmin against fp64 (the comparisons below are teacher-forced on it)
+    R.check_codes(codes, z, R.Params(g_in, v_in, b_in, g_out, v_out, b_out, cb))
     leaves64 = [a.double().requires_grad_() for a in (z, mask, g_in, v_in, b_in, g_out, v_out, b_out, cb)]
     zq64, c64, cb64 = rvq64(*leaves64, codes.cpu())
     assert rel_err(z_q.detach().cpu().numpy(), zq64.detach().numpy()) < TOL
@@ -305,6 +308,47 @@ def test_rvq_backward_vs_torch64(nq, B, T):
         assert e < TOL, f"{nm}: rel {e}"
 
 
+def _rvq_train_forward(params, z, mask):
+    with torch.no_grad():
+        out = train._RvqTrain.apply(z.to(DEV), mask.to(DEV), *(p.to(DEV) for p in params))
+    torch.cuda.synchronize()
+    return out
+
+
+def test_rvq_train_forward_diverse_vs_fp64():
+    """rvq_encode_train's own argmin on inputs that exercise it (tests/rvq_ref.py: 100+ distinct
+    codes per stage, every quarter of the codebook): every decision within 8 eps_d of its
+    stage's fp64 minimum (check_codes), latents and z_q against the fp64 chain on those codes."""
+    nq, B, T = 8, 3, 87
+    params, z, _ = R.diverse_case(nq, 1024, B, T)
+    mask = (torch.rand(B, nq, T, generator=torch.Generator().manual_seed(5)) < 0.7).float()
+    mask[:, 0] = 1.0
+    z_q, _commit, _cbl, codes, lat = _rvq_train_forward(params, z, mask)
+    distinct = R.assert_diverse(codes, 1024)
+    res = R.check_codes(codes, z, params)
+    print(f"train diverse: eps_d={res['eps_d']:.2e} margin={res['margin']:.2e} "
+          f"worst={res['worst']:.2e} mismatch={res['share']:.4%} min distinct={distinct}")
+    ref = res["ref"]
+    assert rel_err(lat.cpu().numpy(), ref.latents.numpy()) < 1e-5
+    zq64 = (ref.z_q_is * mask.double()[:, :, None, :]).sum(1)
+    assert rel_err(z_q.cpu().numpy(), zq64.numpy()) < 1e-5
+
+
+def test_rvq_train_exact_ties_take_lowest_index():
+    """cb[N/2 + j] = cb[j] in every stage: every decision of the training forward is an exact tie
+    of two identical rows and takes the lower index, as the eval kernels do
+    (test_gpu_parity.py test_rvq_exact_ties_take_lowest_index)."""
+    nq, N = 8, 1024
+    params, gen = R.diverse_rvq_params(nq, N, 900 + nq + N)
+    params = params._replace(cb=R.tie_codebook(params.cb, "half"))
+    z = R.diverse_z(2, 87, gen)
+    codes = _rvq_train_forward(params, z, torch.ones(2, nq, 87))[3].cpu()
+    R.check_codes(codes, z, params)
+    high = ~R.lower_twin(codes, N, "half")
+    assert not bool(high.any()), (f"{int(high.sum())} of {codes.numel()} decisions took the "
+                                  f"higher twin, first at {high.nonzero()[0].tolist()}")
+
+
 def _quantizer_leaves(q):
     leaves = [a.detach().double().cpu().requires_grad_() for a in train._stage_params(q.quantizers)]
     return leaves
@@ -314,6 +358,8 @@ def _check_quantizer_train(q, z, out, mask_ref):
     """z_q / losses / gradients of a training-mode quantizer output against rvq64 with the
     reference's mask (codes fixed, as the straight-through estimator uses them)."""
     leaves64 = _quantizer_leaves(q)
+    # the forward's own argmin against fp64 (everything below is teacher-forced on its codes)
+    R.check_codes(out["codes"], z, R.Params(*leaves64))
     z64 = z.detach().double().cpu().requires_grad_()
     zq64, c64, cb64 = rvq64(z64, mask_ref.double(), *leaves64, out["codes"].cpu())
     assert rel_err(out["z_q"].detach().cpu().numpy(), zq64.detach().numpy()) < TOL

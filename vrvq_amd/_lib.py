@@ -92,7 +92,7 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_sync_error": ([_P, _P], _I), "vrvq_rvq_timing": ([_I], _I),
          "vrvq_rvq_timing_read": ([_P, _P], _I), "vrvq_rvq_pending_error": ([_P], _I),
          "vrvq_rvq_debug": ([ctypes.c_uint, ctypes.c_uint], _I),
-         "vrvq_rvq_debug_capacity": ([_I], _I)}
+         "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I)}
 
 _lock = threading.Lock()
 _lib = None
@@ -174,6 +174,14 @@ def rvq_debug_capacity(clips: int) -> int:
     """Test hook: cap the clips per fused launch from partials (0 forces the two launches, -1
     removes the cap). Returns the previous cap."""
     return int(load().vrvq_rvq_debug_capacity(int(clips)))
+
+
+def conv_last_launch() -> dict:
+    """Tile and path of the last conv launch on the MFMA tiles (include/vrvq.h
+    vrvq_conv_last_launch): {BM, BN, KS, x3 (0 fp32-input, 1 chunk, 2 pair), S (split-K parts)}."""
+    out = (ctypes.c_int * 5)()
+    call("vrvq_conv_last_launch", out)
+    return dict(zip(("BM", "BN", "KS", "x3", "S"), (int(v) for v in out)))
 
 
 def rvq_timing(on: bool) -> bool:

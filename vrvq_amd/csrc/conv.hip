@@ -18,6 +18,7 @@
 #include "conv_core.h"
 #include "conv_x3.h"
 #include <stdlib.h>
+#include <atomic>
 
 namespace {
 
@@ -463,6 +464,19 @@ int launch_x3(const ConvArgs& a, int XW, size_t epi, long long nblk, hipStream_t
   return vrvq_launch_status();
 }
 
+// Tile and path of the last MFMA conv launch (vrvq_conv_last_launch, a host-side debug query:
+// the tests assert the path they claim to pin). One word, so concurrent callers never read a
+// torn record: BM (9 bits) | BN << 9 (9) | KS << 18 (5) | x3 << 23 (2) | S << 25 (7).
+std::atomic<unsigned> g_last_launch{0};
+
+int note_launch(int rc, int bm, int bn, int ks, int x3, int S) {
+  if (rc == 0)
+    g_last_launch.store((unsigned)bm | (unsigned)bn << 9 | (unsigned)ks << 18 |
+                        (unsigned)x3 << 23 | (unsigned)(S & 127) << 25,
+                        std::memory_order_relaxed);
+  return rc;
+}
+
 template <int BM, int BN, int WM, int NW, int KS>
 int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
   ConvArgs a = a0;
@@ -489,8 +503,10 @@ int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
     if (a.w3 != nullptr && a.stride == 1 && a.ssh == 0 && XW <= XW_MAX) {
       // pair tiles (conv_x3.h) need whole K-chunks: other Cin run the tile on plain chunks
       int rc = VRVQ_ERR_UNSUPPORTED;
+      int x3 = 1;  // plain chunks | 2: pair chunks
       if (x3_pair<KS, BM, BN>() && a.cin % X3Cfg<KS, true>::CK == 0) {
         constexpr bool kXpf = KS == 7 && x3_pair<KS, BM, BN>();  // the 64 x 256 pair k7 tile
+        x3 = 2;
         if (kXpf && conv_x3_xpf())
           rc = launch_x3<BM, BN, WM, NW, KS, x3_pair<KS, BM, BN>(), false, kXpf>(a, XW, epi, nblk, st);
         else
@@ -498,7 +514,7 @@ int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
       }
       else
         rc = launch_x3<BM, BN, WM, NW, KS, false>(a, XW, epi, nblk, st);
-      if (rc != VRVQ_ERR_UNSUPPORTED) return rc;
+      if (rc != VRVQ_ERR_UNSUPPORTED) return note_launch(rc, BM, BN, KS, x3, 0);
     }
   }
   if (a.psh) return VRVQ_ERR_UNSUPPORTED;  // the phase-split view exists on the x3 loop only
@@ -513,7 +529,7 @@ int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
   }
   hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, NW, KS, false>), dim3((unsigned)nblk),
                      dim3(64 * NW), lds, st, a);
-  return vrvq_launch_status();
+  return note_launch(vrvq_launch_status(), BM, BN, KS, 0, 0);
 }
 
 
@@ -667,7 +683,7 @@ int launch_splitk(const ConvArgs& a0, int batch, int S, hipStream_t st) {
     if (rc) return rc;
     hipLaunchKernelGGL((conv_splitk_epilogue_kernel<128, 96, 4, 4>), dim3((unsigned)tiles),
                        dim3(256), epi, st, a);
-    return vrvq_launch_status();
+    return note_launch(vrvq_launch_status(), 128, 96, KS, KS == 2 ? 2 : 1, S);
   } else {
     (void)a0; (void)batch; (void)S; (void)st;
     return VRVQ_ERR_UNSUPPORTED;
@@ -919,6 +935,17 @@ extern "C" int vrvq_conv1d_workspace(int batch, int cin, int tin, int cout, int 
     S = splitk_parts(cout, cin, (int)tout, k, false, false, x3 != 0);
   }
   *bytes = (long long)splitk_bytes(S, cout, (int)tout, batch);
+  return 0;
+}
+
+extern "C" int vrvq_conv_last_launch(int out[5]) {
+  VRVQ_CHECK_ARG(out);
+  const unsigned v = g_last_launch.load(std::memory_order_relaxed);
+  out[0] = (int)(v & 511);
+  out[1] = (int)(v >> 9 & 511);
+  out[2] = (int)(v >> 18 & 31);
+  out[3] = (int)(v >> 23 & 3);
+  out[4] = (int)(v >> 25 & 127);
   return 0;
 }
 
