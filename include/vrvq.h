@@ -448,6 +448,43 @@ int vrvq_rate_solve(const float* imp, int batch, int frames, int nq, const int* 
 int vrvq_scale_imp_rows(const float* imp, int batch, int frames, const float* levels, float* out,
                         vrvq_stream_t stream);
 
+/* Distortion metrics (models/utils.py:91-129 cal_metrics: torchmetrics' SI-SDR / SI-SNR / SNR
+ * formulas for fp32 input, and the L1 distance), per row and without a host sync.
+ *
+ * est [rows][samples] and ref [ref_rows][samples], rows % ref_rows == 0: row r is compared with
+ * reference row r % ref_rows, the level-major (L * B, T) layout of a level sweep. lengths
+ * [ref_rows] (int64, device) or NULL: only the first n = clamp(lengths[r % ref_rows], 0, samples)
+ * samples of a row count (NULL: n = samples); nothing at or past n is read.
+ *
+ * With p = est, t = ref, every product, difference and sum formed in fp64:
+ *   moments[r][8] = { sum p, sum t, sum p t, sum p^2, sum t^2, sum |p - t|, sum (p - t)^2, n }
+ *   eps = 2^-23 (float32 eps)
+ *   si(pt, pp, tt): alpha = (pt + eps) / (tt + eps), S = alpha^2 tt,
+ *                   N = max(S - 2 alpha pt + pp, 0), 10 log10((S + eps) / (N + eps))
+ *   metrics[r][0] si_sdr = si(sum p t, sum p^2, sum t^2)                      (zero_mean = False)
+ *   metrics[r][1] si_snr = si of the centred moments sum p t - sum p sum t / n,
+ *                          max(sum p^2 - (sum p)^2 / n, 0), max(sum t^2 - (sum t)^2 / n, 0)
+ *   metrics[r][2] snr    = 10 log10((sum t^2 + eps) / (sum (p - t)^2 + eps))
+ *   metrics[r][3] l1     = sum |p - t| / n
+ * n = 0 gives l1 = NaN and 0 dB for the other three; NaN in the data gives NaN out.
+ *
+ * Two launches: workgroups of a fixed VRVQ_METRICS_CHUNK samples (it does not depend on the
+ * shape, the batch or the device) store seven partial sums each to workspace[row][chunk][7];
+ * one wave per row adds them and evaluates the formulas. No atomics, a fixed summation order
+ * per sample index that also does not depend on the rows' addresses: a row's result is the same
+ * bits alone or in any batch. No sequential fp64 summation chain exceeds 4096 terms (64 per
+ * thread, trees over lanes, 4 waves, <= 4096 chunks per lane), which bounds samples at
+ * 2^32 (64 * 4096 chunks); rows <= 65535. Outside those: VRVQ_ERR_ARG.
+ *   vrvq_signal_metrics_workspace  *bytes = rows * ceil(samples / VRVQ_METRICS_CHUNK) * 7 * 8
+ *   vrvq_signal_metrics            metrics [rows][4] fp64; moments [rows][8] fp64 or NULL;
+ *                                  workspace 8-byte aligned, workspace_bytes at least the above */
+#define VRVQ_METRICS_CHUNK 16384
+int vrvq_signal_metrics_workspace(int rows, long long samples, long long* bytes);
+int vrvq_signal_metrics(const float* est, const float* ref, int rows, int ref_rows,
+                        long long samples, const long long* lengths, double* metrics,
+                        double* moments, void* workspace, long long workspace_bytes,
+                        vrvq_stream_t stream);
+
 /* Variable-length code packing from importance masks (the reference's
  * DACFile, models/dac_base.py:19-58, stores the full uint16 code matrix). Packed stream is
  * clip-major, frame-major, stage-minor uint16: packed[clip_off[b] + frame_off[b,t] + i] =

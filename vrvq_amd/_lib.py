@@ -64,6 +64,9 @@ SIGNATURES = {
     "vrvq_rate_curve": [_P, _I, _I, _I, _P, _P, _I, _P, _P],
     "vrvq_rate_solve": [_P, _I, _I, _I, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P],
     "vrvq_scale_imp_rows": [_P, _I, _I, _P, _P, _P],
+    "vrvq_signal_metrics_workspace": [_I, ctypes.c_longlong, _P],
+    "vrvq_signal_metrics": [_P, _P, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, ctypes.c_longlong,
+                            _P],
     "vrvq_pack_counts": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "vrvq_pack_codes": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "vrvq_unpack_offsets": [_P, _I, _I, _P, _P, _P],
@@ -93,6 +96,8 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_timing_read": ([_P, _P], _I), "vrvq_rvq_pending_error": ([_P], _I),
          "vrvq_rvq_debug": ([ctypes.c_uint, ctypes.c_uint], _I),
          "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I)}
+
+METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
 
 _lock = threading.Lock()
 _lib = None

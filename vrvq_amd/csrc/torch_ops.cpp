@@ -741,6 +741,45 @@ Tensor scale_imp_rows(const Tensor& imp, const Tensor& levels) {
   return out;
 }
 
+// --------------------------------------------------------------------------- distortion metrics
+// SI-SDR / SI-SNR / SNR / L1 of every row of est against row r % B of ref (include/vrvq.h
+// "Distortion metrics"; models/utils.py:91-129 cal_metrics on the device). est (R, T) or
+// (R, 1, T), ref (B, T) or (B, 1, T), lengths (B,) int64 or None -> metrics (R, 4), moments
+// (R, 8), both fp64.
+std::tuple<Tensor, Tensor> signal_metrics(const Tensor& est, const Tensor& ref,
+                                          const optional<Tensor>& lengths) {
+  check_t(est, "est");
+  check_on(ref, est, "ref");
+  TORCH_CHECK(est.dim() >= 2 && est.numel() > 0 && est.numel() == est.size(0) * est.size(-1),
+              "signal_metrics: est must be (R, T) or (R, 1, T)");
+  TORCH_CHECK(ref.dim() >= 2 && ref.numel() > 0 && ref.numel() == ref.size(0) * ref.size(-1),
+              "signal_metrics: ref must be (B, T) or (B, 1, T)");
+  const int64_t R = est.size(0), B = ref.size(0), T = est.size(-1);
+  TORCH_CHECK(ref.size(-1) == T, "signal_metrics: est has ", T, " samples, ref ", ref.size(-1));
+  TORCH_CHECK(R % B == 0, "signal_metrics: ", R, " rows are no multiple of ", B,
+              " reference rows");
+  TORCH_CHECK(R < (1LL << 31), "signal_metrics: est too large");
+  if (lengths.has_value()) {
+    check_on(*lengths, est, "lengths", at::kLong);
+    TORCH_CHECK(lengths->dim() == 1 && lengths->numel() == B,
+                "signal_metrics: one length per reference row");
+  }
+  c10::DeviceGuard guard(est.device());
+  long long ws_bytes = 0;
+  check_rc(vrvq_signal_metrics_workspace((int)R, T, &ws_bytes), "vrvq_signal_metrics_workspace");
+  Tensor metrics = at::empty({R, 4}, est.options().dtype(at::kDouble));
+  Tensor moments = at::empty({R, 8}, est.options().dtype(at::kDouble));
+  Tensor ws = at::empty({ws_bytes / 8}, est.options().dtype(at::kDouble));
+  check_rc(vrvq_signal_metrics(
+               est.data_ptr<float>(), ref.data_ptr<float>(), (int)R, (int)B, T,
+               lengths.has_value() ? reinterpret_cast<const long long*>(lengths->data_ptr<int64_t>())
+                                   : nullptr,
+               metrics.data_ptr<double>(), moments.data_ptr<double>(), ws.data_ptr<double>(),
+               ws_bytes, stream_of(est)),
+           "vrvq_signal_metrics");
+  return {metrics, moments};
+}
+
 // --------------------------------------------------------------------------- code packing
 // Variable-length packing. The packed length is data-dependent, so
 // pack_codes takes it from the host (vrvq_amd/codes_io.py reads clip_off[B]).
@@ -1191,6 +1230,9 @@ TORCH_LIBRARY(vrvq, m) {
       "rate_solve(Tensor imp, Tensor bits, Tensor group_off, Tensor budget, float level_lo, "
       "float level_hi) -> (Tensor, Tensor, Tensor)");
   m.def("scale_imp_rows(Tensor imp, Tensor levels) -> Tensor");
+  m.def(
+      "signal_metrics(Tensor est, Tensor ref, Tensor? lengths) "
+      "-> (Tensor metrics, Tensor moments)");
   m.def("pack_counts(Tensor mask) -> (Tensor, Tensor, Tensor)");
   m.def(
       "pack_codes(Tensor codes, Tensor counts, Tensor clip_off, int total, int ncode) "
@@ -1253,6 +1295,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("rate_curve", &rate_curve); \
   m.impl("rate_solve", &rate_solve); \
   m.impl("scale_imp_rows", &scale_imp_rows); \
+  m.impl("signal_metrics", &signal_metrics); \
   m.impl("pack_counts", &pack_counts); \
   m.impl("pack_codes", &pack_codes); \
   m.impl("unpack_offsets", &unpack_offsets); \

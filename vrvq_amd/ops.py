@@ -311,6 +311,15 @@ def scale_imp_rows(imp: torch.Tensor, levels: torch.Tensor) -> torch.Tensor:
     return _ops().scale_imp_rows(imp, levels)
 
 
+def signal_metrics(est: torch.Tensor, ref: torch.Tensor,
+                   lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Distortion of every row of est (R, T) or (R, 1, T) against row r % B of ref (B, T) or
+    (B, 1, T), over the first lengths[r % B] samples (int64 (B,), or None for all): float64
+    metrics (R, 4) = si_sdr, si_snr, snr, l1 and moments (R, 8), in two launches and without a
+    host sync (include/vrvq.h "Distortion metrics")."""
+    return _ops().signal_metrics(est, ref, lengths)
+
+
 # ----------------------------------------------------------------------------- training step
 # Backward operators of the generator (include/vrvq.h "Training step"; vrvq_amd/train.py).
 def conv1d_wgrad(a, x, k: int, stride: int = 1, pad: int = 0, dil: int = 1,
@@ -525,6 +534,12 @@ def _register_fakes():
     @reg("vrvq::scale_imp_rows")
     def _(imp, levels):
         return torch.empty_like(imp)
+
+    @reg("vrvq::signal_metrics")
+    def _(est, ref, lengths):
+        R = est.shape[0]
+        return (est.new_empty((R, 4), dtype=torch.float64),
+                est.new_empty((R, 8), dtype=torch.float64))
 
     @reg("vrvq::pack_counts")
     def _(mask):
