@@ -485,6 +485,60 @@ int vrvq_signal_metrics(const float* est, const float* ref, int rows, int ref_ro
                         double* moments, void* workspace, long long workspace_bytes,
                         vrvq_stream_t stream);
 
+/* Spectral distance (models/loss.py:168-401 MultiScaleSTFTLoss / MelSpectrogramLoss, levels=None),
+ * per row and per scale and without a host sync; no spectrogram reaches memory.
+ *
+ * est [rows][samples], ref [ref_rows][samples], rows % ref_rows == 0, lengths [ref_rows] (int64,
+ * device) or NULL: rows pair up and lengths count as in vrvq_signal_metrics; a row of length n is
+ * measured as if both signals ended after n samples. For one row (e against r, n samples) and one
+ * scale s with window W = windows[s] (a power of two in [32, 2048]) and n_mels[s]:
+ *   hop = W / 4, frames = 1 + n / hop; frame j holds samples j hop - W/2 .. j hop + W/2 - 1,
+ *   indices outside [0, n) reflected without repeating the edge (-i -> i, n-1+i -> n-1-i):
+ *   torch.stft(center=True, pad_mode="reflect"), which needs n > W / 2;
+ *   window: periodic Hann 0.5 - 0.5 cos(2 pi k / W), no normalisation; magnitudes |rfft| of
+ *   bins 0 .. W/2 in fp32;
+ *   n_mels[s] > 0: E[m] = sum_j weights[off[m] + j] * |X[start[m] + j]|, j < len[m], in ascending
+ *   j (fp32 fma chain), the banded form of a mel filter bank whose rows are contiguous runs;
+ *   n_mels[s] == 0: the W/2 + 1 linear bins;
+ *   terms[row][s][0] = mean |pow log10(max(E, clamp_eps)) - pow log10(max(R, clamp_eps))|
+ *   terms[row][s][1] = mean |E - R|
+ * both in fp64 over all (element, frame) pairs of the row. A row with n <= W / 2 gets NaN in both
+ * terms of that scale; NaN in a row's data gives NaN in that row.
+ *   distance[row] = sum_s (log_weight terms[row][s][0] + mag_weight terms[row][s][1]), the
+ * scales added in their order in fp64 (NaN if any scale is); distance may be NULL.
+ *
+ * Caller-owned device tables, per scale:
+ *   tables[s]        3 W floats, 8-byte aligned: exp(-2 pi i k / W) as (re, im) pairs, k < W, then
+ *                    the W window values; built in fp64 and rounded once to fp32
+ *   bands[s]         3 n_mels int32: start[m], len[m], off[m] (start[m] + len[m] <= W/2 + 1, off[m]
+ *                    the band's first entry of band_weights[s]); unused for n_mels[s] == 0
+ *   band_weights[s]  the bands' fp32 weights, packed
+ * windows, n_mels, tables, bands, band_weights are host arrays of n_scales (<= 16) entries.
+ *
+ * n_scales + 1 launches on `stream`, no atomics. A workgroup owns a tile of
+ * VRVQ_SPECTRAL_TILE_FRAMES(W) consecutive frames of one (row, scale) and stores two partial sums
+ * to workspace; one wave per (row, scale) adds the tiles in a fixed order. The order in which an
+ * element is added is a function of (scale, frame, element) alone: a row's bits do not depend on
+ * the other rows, on their number, or on the row's address.
+ * VRVQ_ERR_ARG before any launch: null pointers, a window that is no power of two in [32, 2048],
+ * n_mels[s] < 0 or > W/2 + 1, n_scales outside [1, 16], rows outside [1, 65535], ref_rows <= 0 or
+ * rows % ref_rows != 0, samples outside [1, 2^32], samples <= max(W) / 2 without lengths,
+ * clamp_eps <= 0, a workspace too small or not 8-byte aligned.
+ *   vrvq_spectral_distance_workspace  *bytes = 16 * rows * sum_s ceil((1 + samples / hop_s) /
+ *                                     VRVQ_SPECTRAL_TILE_FRAMES(W_s))
+ *   vrvq_spectral_distance            terms [rows][n_scales][2] fp64, distance [rows] fp64 or NULL */
+#define VRVQ_SPECTRAL_TILE_SAMPLES 8192
+#define VRVQ_SPECTRAL_TILE_FRAMES(window) (VRVQ_SPECTRAL_TILE_SAMPLES / (window))
+int vrvq_spectral_distance_workspace(int rows, long long samples, int n_scales, const int* windows,
+                                     long long* bytes);
+int vrvq_spectral_distance(const float* est, const float* ref, int rows, int ref_rows,
+                           long long samples, const long long* lengths, int n_scales,
+                           const int* windows, const int* n_mels, const float* const* tables,
+                           const int* const* bands, const float* const* band_weights,
+                           double clamp_eps, double pow, double log_weight, double mag_weight,
+                           double* terms, double* distance, void* workspace,
+                           long long workspace_bytes, vrvq_stream_t stream);
+
 /* Variable-length code packing from importance masks (the reference's
  * DACFile, models/dac_base.py:19-58, stores the full uint16 code matrix). Packed stream is
  * clip-major, frame-major, stage-minor uint16: packed[clip_off[b] + frame_off[b,t] + i] =

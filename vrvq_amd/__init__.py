@@ -10,7 +10,8 @@ from .layers import (DecoderBlock, EncoderBlock, ResidualUnit, Snake1d, WNConv1d
                      WNConvTranspose1d)
 from .utils import (cal_bpf_from_mask, cal_bpf_tensor, check_errors, generate_mask_hard,
                     generate_mask_ste, kbps_to_budget, level_sweep, masked_sum, rate_curve,
-                    rd_sweep, scale_importance, signal_metrics, solve_levels, solve_quality)
+                    mel_distance, rd_sweep, scale_importance, signal_metrics, solve_levels,
+                    solve_quality, spectral_distance, stft_distance)
 from .config import from_config, load_config, model_kwargs
 
 __all__ = [
@@ -20,5 +21,6 @@ __all__ = [
     "generate_mask_hard", "generate_mask_ste", "cal_bpf_from_mask", "cal_bpf_tensor",
     "masked_sum", "scale_importance", "level_sweep", "load_config", "model_kwargs",
     "from_config", "check_errors", "rate_curve", "solve_levels", "kbps_to_budget",
-    "signal_metrics", "rd_sweep", "solve_quality",
+    "signal_metrics", "rd_sweep", "solve_quality", "spectral_distance", "mel_distance",
+    "stft_distance",
 ]

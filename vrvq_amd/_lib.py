@@ -67,6 +67,10 @@ SIGNATURES = {
     "vrvq_signal_metrics_workspace": [_I, ctypes.c_longlong, _P],
     "vrvq_signal_metrics": [_P, _P, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, ctypes.c_longlong,
                             _P],
+    "vrvq_spectral_distance_workspace": [_I, ctypes.c_longlong, _I, _P, _P],
+    "vrvq_spectral_distance": [_P, _P, _I, _I, ctypes.c_longlong, _P, _I, _P, _P, _P, _P, _P,
+                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                               _P, _P, _P, ctypes.c_longlong, _P],
     "vrvq_pack_counts": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "vrvq_pack_codes": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "vrvq_unpack_offsets": [_P, _I, _I, _P, _P, _P],
@@ -98,6 +102,12 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I)}
 
 METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
+SPECTRAL_TILE_SAMPLES = 8192  # VRVQ_SPECTRAL_TILE_SAMPLES (tests/test_spectral.py compares)
+
+
+def spectral_tile_frames(window: int) -> int:
+    """Frames of one workgroup's tile at this window: VRVQ_SPECTRAL_TILE_FRAMES of the header."""
+    return SPECTRAL_TILE_SAMPLES // int(window)
 
 _lock = threading.Lock()
 _lib = None

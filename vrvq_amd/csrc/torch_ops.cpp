@@ -19,6 +19,8 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <vector>
+
 #include "../../include/vrvq.h"
 
 namespace {
@@ -780,6 +782,76 @@ std::tuple<Tensor, Tensor> signal_metrics(const Tensor& est, const Tensor& ref,
   return {metrics, moments};
 }
 
+// --------------------------------------------------------------------------- spectral distance
+// The log and magnitude terms of MultiScaleSTFTLoss / MelSpectrogramLoss (models/loss.py:168-401)
+// per row and scale (include/vrvq.h "Spectral distance"). est (R, T) or (R, 1, T), ref (B, T) or
+// (B, 1, T), lengths (B,) int64 or None; per scale tables (3 W,) float32, bands (3, n_mels) int32
+// and weights float32 (both empty for n_mels == 0) -> terms (R, S, 2) and distance (R,), fp64.
+std::tuple<Tensor, Tensor> spectral_distance(const Tensor& est, const Tensor& ref, const optional<Tensor>& lengths,
+                         at::IntArrayRef windows, at::IntArrayRef n_mels, at::TensorList tables,
+                         at::TensorList bands, at::TensorList weights, double clamp_eps,
+                         double pow, double log_weight, double mag_weight) {
+  check_t(est, "est");
+  check_on(ref, est, "ref");
+  TORCH_CHECK(est.dim() >= 2 && est.numel() > 0 && est.numel() == est.size(0) * est.size(-1),
+              "spectral_distance: est must be (R, T) or (R, 1, T)");
+  TORCH_CHECK(ref.dim() >= 2 && ref.numel() > 0 && ref.numel() == ref.size(0) * ref.size(-1),
+              "spectral_distance: ref must be (B, T) or (B, 1, T)");
+  const int64_t R = est.size(0), B = ref.size(0), T = est.size(-1);
+  TORCH_CHECK(ref.size(-1) == T, "spectral_distance: est has ", T, " samples, ref ",
+              ref.size(-1));
+  TORCH_CHECK(R % B == 0, "spectral_distance: ", R, " rows are no multiple of ", B,
+              " reference rows");
+  TORCH_CHECK(R < (1LL << 31), "spectral_distance: est too large");
+  if (lengths.has_value()) {
+    check_on(*lengths, est, "lengths", at::kLong);
+    TORCH_CHECK(lengths->dim() == 1 && lengths->numel() == B,
+                "spectral_distance: one length per reference row");
+  }
+  const size_t S = windows.size();
+  TORCH_CHECK(S >= 1 && S <= 16 && n_mels.size() == S && tables.size() == S && bands.size() == S &&
+                  weights.size() == S,
+              "spectral_distance: 1 to 16 scales, one n_mels, tables, bands and weights each");
+  std::vector<int> win(S), nm(S);
+  std::vector<const float*> tab(S), wts(S);
+  std::vector<const int*> bnd(S);
+  for (size_t s = 0; s < S; ++s) {
+    const int64_t W = windows[s], M = n_mels[s];
+    TORCH_CHECK(W >= 32 && W <= 2048 && (W & (W - 1)) == 0, "spectral_distance: window ", W,
+                " is no power of two in [32, 2048]");
+    TORCH_CHECK(M >= 0 && M <= W / 2 + 1, "spectral_distance: n_mels ", M, " for window ", W);
+    check_on(tables[s], est, "tables");
+    TORCH_CHECK(tables[s].numel() == 3 * W, "spectral_distance: tables[", s, "] must hold 3 W");
+    if (M > 0) {
+      check_on(bands[s], est, "bands", at::kInt);
+      check_on(weights[s], est, "weights");
+      TORCH_CHECK(bands[s].numel() == 3 * M, "spectral_distance: bands[", s, "] must be (3, ", M,
+                  ")");
+    }
+    win[s] = (int)W;
+    nm[s] = (int)M;
+    tab[s] = tables[s].data_ptr<float>();
+    bnd[s] = M > 0 ? bands[s].data_ptr<int>() : nullptr;
+    wts[s] = M > 0 ? weights[s].data_ptr<float>() : nullptr;
+  }
+  c10::DeviceGuard guard(est.device());
+  long long ws_bytes = 0;
+  check_rc(vrvq_spectral_distance_workspace((int)R, T, (int)S, win.data(), &ws_bytes),
+           "vrvq_spectral_distance_workspace");
+  Tensor terms = at::empty({R, (int64_t)S, 2}, est.options().dtype(at::kDouble));
+  Tensor distance = at::empty({R}, est.options().dtype(at::kDouble));
+  Tensor ws = at::empty({ws_bytes / 8}, est.options().dtype(at::kDouble));
+  check_rc(vrvq_spectral_distance(
+               est.data_ptr<float>(), ref.data_ptr<float>(), (int)R, (int)B, T,
+               lengths.has_value() ? reinterpret_cast<const long long*>(lengths->data_ptr<int64_t>())
+                                   : nullptr,
+               (int)S, win.data(), nm.data(), tab.data(), bnd.data(), wts.data(), clamp_eps, pow,
+               log_weight, mag_weight, terms.data_ptr<double>(), distance.data_ptr<double>(),
+               ws.data_ptr<double>(), ws_bytes, stream_of(est)),
+           "vrvq_spectral_distance");
+  return {terms, distance};
+}
+
 // --------------------------------------------------------------------------- code packing
 // Variable-length packing. The packed length is data-dependent, so
 // pack_codes takes it from the host (vrvq_amd/codes_io.py reads clip_off[B]).
@@ -1233,6 +1305,10 @@ TORCH_LIBRARY(vrvq, m) {
   m.def(
       "signal_metrics(Tensor est, Tensor ref, Tensor? lengths) "
       "-> (Tensor metrics, Tensor moments)");
+  m.def(
+      "spectral_distance(Tensor est, Tensor ref, Tensor? lengths, int[] windows, int[] n_mels, "
+      "Tensor[] tables, Tensor[] bands, Tensor[] weights, float clamp_eps, float pow, "
+      "float log_weight, float mag_weight) -> (Tensor terms, Tensor distance)");
   m.def("pack_counts(Tensor mask) -> (Tensor, Tensor, Tensor)");
   m.def(
       "pack_codes(Tensor codes, Tensor counts, Tensor clip_off, int total, int ncode) "
@@ -1296,6 +1372,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("rate_solve", &rate_solve); \
   m.impl("scale_imp_rows", &scale_imp_rows); \
   m.impl("signal_metrics", &signal_metrics); \
+  m.impl("spectral_distance", &spectral_distance); \
   m.impl("pack_counts", &pack_counts); \
   m.impl("pack_codes", &pack_codes); \
   m.impl("unpack_offsets", &unpack_offsets); \

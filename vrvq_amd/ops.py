@@ -320,6 +320,21 @@ def signal_metrics(est: torch.Tensor, ref: torch.Tensor,
     return _ops().signal_metrics(est, ref, lengths)
 
 
+def spectral_distance(est: torch.Tensor, ref: torch.Tensor, lengths: Optional[torch.Tensor],
+                      windows, n_mels, tables, bands, weights, clamp_eps: float, pow: float,
+                      log_weight: float = 1.0,
+                      mag_weight: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The log and magnitude terms of the multi-scale STFT / mel distance of every row of est
+    (R, T) or (R, 1, T) against row r % B of ref, per scale, float64 terms (R, S, 2), and their
+    weighted sum over the scales, float64 distance (R,), in S + 1 launches and without a host sync. tables / bands / weights: per scale the twiddle-and-window
+    table, the mel bands and their weights (include/vrvq.h "Spectral distance";
+    vrvq_amd.utils.spectral_distance builds and caches them)."""
+    return _ops().spectral_distance(est, ref, lengths, [int(w) for w in windows],
+                                    [int(m) for m in n_mels], list(tables), list(bands),
+                                    list(weights), float(clamp_eps), float(pow),
+                                    float(log_weight), float(mag_weight))
+
+
 # ----------------------------------------------------------------------------- training step
 # Backward operators of the generator (include/vrvq.h "Training step"; vrvq_amd/train.py).
 def conv1d_wgrad(a, x, k: int, stride: int = 1, pad: int = 0, dil: int = 1,
@@ -540,6 +555,12 @@ def _register_fakes():
         R = est.shape[0]
         return (est.new_empty((R, 4), dtype=torch.float64),
                 est.new_empty((R, 8), dtype=torch.float64))
+
+    @reg("vrvq::spectral_distance")
+    def _(est, ref, lengths, windows, n_mels, tables, bands, weights, clamp_eps, pow,
+          log_weight, mag_weight):
+        return (est.new_empty((est.shape[0], len(windows), 2), dtype=torch.float64),
+                est.new_empty((est.shape[0],), dtype=torch.float64))
 
     @reg("vrvq::pack_counts")
     def _(mask):

@@ -2,6 +2,7 @@
 scripts/inference.py:88-112) on gfx950 kernels."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import Sequence
 
@@ -236,6 +237,170 @@ def signal_metrics(est: torch.Tensor, ref: torch.Tensor, lengths=None) -> dict:
     return out
 
 
+# ------------------------------------------------------------------ spectral distances
+SPECTRAL_METRICS = ("mel", "stft")     # distances, smaller is better: rd_sweep columns, solve_quality
+MEL_DISTANCE = dict(windows=(2048, 512), n_mels=(150, 80), clamp_eps=1e-5, pow=2.0,
+                    log_weight=1.0, mag_weight=1.0)    # models/loss.py:257 MelSpectrogramLoss()
+STFT_DISTANCE = dict(windows=(2048, 512), n_mels=None, clamp_eps=1e-5, pow=2.0,
+                     log_weight=1.0, mag_weight=1.0)   # models/loss.py:168 MultiScaleSTFTLoss()
+SPECTRAL_MIN_SAMPLES = 1025            # both defaults' largest window is 2048: T > 1024
+
+
+@functools.lru_cache(maxsize=None)
+def spectral_tables(window: int) -> np.ndarray:
+    """(3 W,) float32 of include/vrvq.h "Spectral distance": exp(-2 pi i k / W) as (re, im) pairs,
+    then the periodic Hann window, both formed in float64 and rounded once."""
+    ang = 2.0 * np.pi * np.arange(window, dtype=np.float64) / window
+    tw = np.stack([np.cos(ang), -np.sin(ang)], axis=1).reshape(-1)
+    return np.concatenate([tw, 0.5 - 0.5 * np.cos(ang)]).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def mel_bands(sample_rate: int, window: int, n_mels: int, fmin: float = 0.0, fmax=None):
+    """The banded form of losses.mel_filters: (bands (3, n_mels) int32 = start, len, offset into
+    the weights; weights float32, the rows' non-zero runs packed, fp32 values as they are).
+    ValueError if a row's non-zeros are not one contiguous run (then the banded sum would not be
+    the dense one)."""
+    from .losses import mel_filters
+    fb = mel_filters(int(sample_rate), int(window), int(n_mels), float(fmin),
+                     None if fmax is None else float(fmax))
+    bands, weights, off = np.zeros((3, n_mels), np.int32), [], 0
+    for m, row in enumerate(fb):
+        nz = np.flatnonzero(row)
+        start, ln = (int(nz[0]), int(nz[-1] - nz[0] + 1)) if nz.size else (0, 0)
+        if nz.size != ln:
+            raise ValueError(f"mel filter {m} of ({window}, {n_mels}) is not one contiguous run")
+        bands[:, m] = (start, ln, off)
+        weights.append(row[start:start + ln])
+        off += ln
+    weights = np.concatenate(weights + [np.zeros(1, np.float32)]).astype(np.float32)
+    return bands, weights
+
+
+_spectral_cache: dict = {}
+
+
+def _spectral_device_tables(device, sample_rate, windows, n_mels, fmin, fmax):
+    """Per scale the device buffers of ops.spectral_distance, built once per (device,
+    configuration) and kept. The first call of a configuration copies from the host, so it cannot
+    be inside a stream capture; later calls can."""
+    tables, bands, weights = [], [], []
+    for w, m, lo, hi in zip(windows, n_mels, fmin, fmax):
+        key = (str(device), w)
+        if key not in _spectral_cache:
+            _spectral_cache[key] = torch.from_numpy(spectral_tables(w)).to(device)
+        tables.append(_spectral_cache[key])
+        key = (str(device), sample_rate, w, m, lo, hi)
+        if key not in _spectral_cache:
+            if m > 0:
+                b, wt = mel_bands(sample_rate, w, m, lo, hi)
+                _spectral_cache[key] = (torch.from_numpy(b).to(device),
+                                        torch.from_numpy(wt).to(device))
+            else:
+                _spectral_cache[key] = (torch.empty(0, dtype=torch.int32, device=device),
+                                        torch.empty(0, dtype=torch.float32, device=device))
+        bands.append(_spectral_cache[key][0])
+        weights.append(_spectral_cache[key][1])
+    return tables, bands, weights
+
+
+def _rows_2d(x: torch.Tensor, what: str) -> torch.Tensor:
+    if not torch.is_tensor(x) or x.dim() < 2 or x.numel() == 0 \
+            or x.numel() != x.shape[0] * x.shape[-1]:
+        raise ValueError(f"spectral_distance: {what} must be (rows, T) or (rows, 1, T)")
+    return x.reshape(x.shape[0], x.shape[-1]).contiguous()
+
+
+def _per_scale(value, default, scales: int, what: str) -> list:
+    if value is None:
+        return [default] * scales
+    value = list(value) if isinstance(value, (list, tuple)) else [value] * scales
+    if len(value) != scales:
+        raise ValueError(f"spectral_distance: {len(value)} {what} for {scales} windows")
+    return value
+
+
+def spectral_distance(est: torch.Tensor, ref: torch.Tensor, *, windows, n_mels=None,
+                      clamp_eps: float = 1e-5, pow: float = 2.0, log_weight: float = 1.0,
+                      mag_weight: float = 1.0, mel_fmin=None, mel_fmax=None,
+                      sample_rate: int = 44100, lengths=None) -> dict:
+    """Multi-scale STFT or mel distance of reconstructions against their inputs, per row, on the
+    device and without a host sync: per clip what models/loss.py:168-401 (MultiScaleSTFTLoss;
+    MelSpectrogramLoss with levels=None) averages over the batch (include/vrvq.h "Spectral
+    distance": hop = window / 4, centred frames with reflection, periodic Hann, |rfft|, optional
+    Slaney mel projection, L1 of pow * log10 of the clamped magnitudes and L1 of the magnitudes,
+    every mean in fp64). With rows of equal length the batch mean of "distance" is the reference
+    loss.
+
+    est is (R, T) or (R, 1, T), ref (B, T) or (B, 1, T) with R = L * B level-major as in
+    signal_metrics; `windows` powers of two in [32, 2048]; `n_mels` one per window (0 or None: the
+    linear bins); `lengths`, one per clip, measures each clip as if it ended there (a clip no
+    longer than window / 2 gets NaN at that scale and in its distance). Returns "distance" (L, B),
+    "log" and "mag" (L, B, S), float64. Argument errors are ValueErrors before any launch."""
+    windows = [int(w) for w in (windows if isinstance(windows, (list, tuple)) else [windows])]
+    S = len(windows)
+    if not 1 <= S <= 16:
+        raise ValueError("spectral_distance: 1 to 16 windows")
+    mels = [int(m or 0) for m in _per_scale(n_mels, 0, S, "n_mels")]
+    fmin = [float(v) for v in _per_scale(mel_fmin, 0.0, S, "mel_fmin")]
+    fmax = [None if v is None else float(v) for v in _per_scale(mel_fmax, None, S, "mel_fmax")]
+    for w, m in zip(windows, mels):
+        if not (32 <= w <= 2048 and w & (w - 1) == 0):
+            raise ValueError(f"spectral_distance: window {w} is no power of two in [32, 2048]")
+        if not 0 <= m <= w // 2 + 1:
+            raise ValueError(f"spectral_distance: n_mels {m} for window {w}")
+    if not float(clamp_eps) > 0:
+        raise ValueError("spectral_distance: clamp_eps must be > 0")
+    e, r = _rows_2d(est, "est"), _rows_2d(ref, "ref")
+    (R, T), B = e.shape, r.shape[0]
+    if r.shape[1] != T or R % B:
+        raise ValueError(f"spectral_distance: est {tuple(est.shape)} against ref "
+                         f"{tuple(ref.shape)}")
+    if lengths is None and T <= max(windows) // 2:
+        raise ValueError(f"spectral_distance: {T} samples; window {max(windows)} needs more than "
+                         f"{max(windows) // 2}")
+    lengths = _clip_lengths(lengths, B, e.device)
+    tables, bands, weights = _spectral_device_tables(e.device, int(sample_rate), windows, mels,
+                                                     fmin, fmax)
+    terms, dist = ops.spectral_distance(e, r, lengths, windows, mels, tables, bands, weights,
+                                        clamp_eps, pow, log_weight, mag_weight)
+    L = R // B
+    return {"distance": dist.reshape(L, B), "log": terms[:, :, 0].reshape(L, B, S),
+            "mag": terms[:, :, 1].reshape(L, B, S)}
+
+
+def mel_distance(est: torch.Tensor, ref: torch.Tensor, sample_rate: int = 44100,
+                 lengths=None) -> torch.Tensor:
+    """The "mel distance" of the DAC-family papers per clip, (L, B) float64: spectral_distance with
+    the defaults of models/loss.py:257 MelSpectrogramLoss (MEL_DISTANCE: n_mels (150, 80), windows
+    (2048, 512), pow 2, log and magnitude terms with weight 1). Needs more than 1024 samples."""
+    return spectral_distance(est, ref, sample_rate=sample_rate, lengths=lengths,
+                             **MEL_DISTANCE)["distance"]
+
+
+def stft_distance(est: torch.Tensor, ref: torch.Tensor, lengths=None) -> torch.Tensor:
+    """The multi-scale STFT distance per clip, (L, B) float64: spectral_distance with the defaults
+    of models/loss.py:168 MultiScaleSTFTLoss (STFT_DISTANCE: windows (2048, 512), linear bins,
+    pow 2, weights 1). Needs more than 1024 samples."""
+    return spectral_distance(est, ref, lengths=lengths, **STFT_DISTANCE)["distance"]
+
+
+def _spectral_columns(spectral) -> tuple:
+    if spectral is None:
+        return ()
+    cols = (spectral,) if isinstance(spectral, str) else tuple(spectral)
+    for c in cols:
+        if c not in SPECTRAL_METRICS:
+            raise ValueError(f"spectral column {c!r} is not one of {SPECTRAL_METRICS}")
+    return cols
+
+
+def _spectral_metric(name: str, recon, x, sample_rate: int, lengths) -> torch.Tensor:
+    if name == "mel":
+        return mel_distance(recon, x, sample_rate, lengths)
+    return stft_distance(recon, x, lengths)
+
+
 def _check_vbr_eval(model, what: str) -> None:
     if getattr(model, "model_type", None) != "VBR":
         raise ValueError(f"{what} needs a VBR model (this one is CBR)")
@@ -255,7 +420,7 @@ def _decoded(model, z_all: torch.Tensor, cap, samples: int, what: str) -> torch.
 
 
 def rd_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_codebook=10,
-             lengths=None, max_decode_clips: int | None = None) -> dict:
+             lengths=None, max_decode_clips: int | None = None, spectral=None) -> dict:
     """Rate-distortion curves of every clip: the table scripts/inference.py:95-122 writes
     (metadata.json, {"sisdr", "kbps"} per level), per clip and with the distortion computed on
     the device.
@@ -270,11 +435,21 @@ def rd_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_codeb
     Returns "levels" (L,) float32, "bpf" (L, B) float32, "kbps" (L, B) float64, "si_sdr",
     "si_snr", "snr", "l1" (L, B) float64 and "moments" (L, B, 8) on the device, "recon"
     (L * B, 1, T), and "summary", the reference's table: per level {"level", "level_scaled",
-    "sisdr", "kbps"} with the batch means. One host sync, the check_errors at the end."""
+    "sisdr", "kbps"} with the batch means. One host sync, the check_errors at the end.
+
+    `spectral` (default None: nothing added) names spectral distances to measure as well, "mel"
+    (mel_distance, the paper's other distortion axis) and / or "stft" (stft_distance): each adds
+    an (L, B) float64 entry of that name, computed from the same `recon`, input and `lengths`,
+    and its batch mean under the same name in every summary row. They need clips of more than
+    1024 samples."""
     _check_vbr_eval(model, "rd_sweep")
     levels = [float(v) for v in levels]
     if not levels:
         raise ValueError("rd_sweep: no levels")
+    spectral = _spectral_columns(spectral)
+    if spectral and audio.shape[-1] < SPECTRAL_MIN_SAMPLES:
+        raise ValueError(f"rd_sweep: spectral distances need clips of at least "
+                         f"{SPECTRAL_MIN_SAMPLES} samples")
     n_q = model.n_codebooks
     with torch.no_grad():
         x = model.preprocess(audio, model.sample_rate)
@@ -283,14 +458,20 @@ def rd_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_codeb
         _masks, z_all = sweep_latents(enc["imp_map"], enc["z_q_is"], levels, n_q)
         recon = _decoded(model, z_all, max_decode_clips, x.shape[-1], "rd_sweep")
         out = signal_metrics(recon, x, lengths)
+        for name in spectral:
+            out[name] = _spectral_metric(name, recon, x, model.sample_rate, lengths)
         bpf = rate_curve(enc["imp_map"], levels, n_q, bits_per_codebook).t().contiguous()
         kbps = bpf.to(torch.float64) * (math.floor(model.sample_rate / model.hop_length) / 1000)
         sisdr_mean, kbps_mean = out["si_sdr"].mean(1), kbps.mean(1)
+        spectral_means = [out[name].mean(1) for name in spectral]
     check_errors(audio.device)  # the sweep's one encode: a timed-out hand-off raises here
     out.update(levels=_device_const(levels, torch.float32, x.device), bpf=bpf, kbps=kbps,
                recon=recon)
     out["summary"] = [{"level": lv, "level_scaled": lv * n_q, "sisdr": s, "kbps": k}
                       for lv, s, k in zip(levels, sisdr_mean.tolist(), kbps_mean.tolist())]
+    for name, means in zip(spectral, spectral_means):
+        for row, v in zip(out["summary"], means.tolist()):
+            row[name] = v
     return out
 
 
@@ -342,10 +523,14 @@ def _quality_args(model, audio, min_db, metric: str, iters: int) -> torch.Tensor
     q = model.quantizer
     if q.level_min is None or q.level_max is None:
         raise ValueError("solve_quality: the model needs level_min and level_max")
-    if metric not in QUALITY_METRICS:
-        raise ValueError(f"solve_quality: metric {metric!r} is not one of {QUALITY_METRICS}")
+    if metric not in QUALITY_METRICS + SPECTRAL_METRICS:
+        raise ValueError(f"solve_quality: metric {metric!r} is not one of "
+                         f"{QUALITY_METRICS + SPECTRAL_METRICS}")
     if int(iters) < 0:
         raise ValueError("solve_quality: iters must be >= 0")
+    if metric in SPECTRAL_METRICS and audio.shape[-1] < SPECTRAL_MIN_SAMPLES:
+        raise ValueError(f"solve_quality: metric {metric!r} needs clips of at least "
+                         f"{SPECTRAL_MIN_SAMPLES} samples")
     B = audio.shape[0]
     if torch.is_tensor(min_db) and min_db.dim() > 0:
         n, target = min_db.numel(), min_db.reshape(-1).to(audio.device, torch.float64)
@@ -383,9 +568,20 @@ def solve_quality(model, audio: torch.Tensor, min_db, metric: str = "si_sdr", it
     target is not reached even at level_max (level = level_lo = level_max), 2 level_min already
     reaches it (level = level_lo = level_min); and "bpf" (B,) float32, "kbps" (B,) float64,
     "mask_imp", "z_q", "codes", "recon" at "level" (encode(level=out["level"]) gives the same
-    mask)."""
+    mask).
+
+    metric "mel" or "stft" (mel_distance / stft_distance, clips of more than 1024 samples): a
+    distance, smaller is better, so `min_db` is then an upper bound on it and the contract is
+    flipped: status 0 means value <= target < value_lo (or value_lo is NaN), status 1 that even
+    level_max stays above the target, status 2 that level_min is already within it. The bisection
+    is the same, run on the negated distance; "value" and "value_lo" are the distances
+    themselves."""
     target = _quality_args(model, audio, min_db, metric, iters)
-    col = METRICS.index(metric)
+    flipped = metric in SPECTRAL_METRICS
+    if flipped:
+        target = -target
+    else:
+        col = METRICS.index(metric)
     nq, q = model.n_codebooks, model.quantizer
     with torch.no_grad():
         x = model.preprocess(audio, model.sample_rate)
@@ -398,6 +594,9 @@ def solve_quality(model, audio: torch.Tensor, min_db, metric: str = "si_sdr", it
 
         def measure(z_q):
             recon = _decoded(model, z_q, None, x.shape[-1], "solve_quality")
+            if flipped:  # (L, B) level-major rows -> one value per row, negated: larger is better
+                return recon, -_spectral_metric(metric, recon, x, model.sample_rate,
+                                                lengths).reshape(-1)
             return recon, ops.signal_metrics(recon, x, lengths)[0][:, col]
 
         ends = torch.cat([_latents_at(imp, z_q_is, lv, nq)[2] for lv in (level_max, level_min)])
@@ -413,6 +612,8 @@ def solve_quality(model, audio: torch.Tensor, min_db, metric: str = "si_sdr", it
         recon, value_hi = measure(z_q)
         bpf = rate_curve(rows, [1.0], nq)[:, 0].contiguous()  # the rows carry their levels
         kbps = bpf.to(torch.float64) * (math.floor(model.sample_rate / model.hop_length) / 1000)
+        if flipped:
+            value_hi, value_lo = -value_hi, -value_lo
     return {"level": hi, "value": value_hi, "level_lo": lo, "value_lo": value_lo,
             "status": status, "bpf": bpf, "kbps": kbps, "mask_imp": mask, "z_q": z_q,
             "codes": enc["codes"], "recon": recon}
