@@ -161,6 +161,20 @@ int vrvq_conv1d_proj(const float* x, int batch, int cin, int tin, const float* a
  * The tests use it to assert the tile they claim to pin. */
 int vrvq_conv_last_launch(int out[5]);
 
+/* Debug query (host only, touches no device; library version 104): what a conv call of this
+ * shape would launch, decided by the code that launches it, and the status that call would
+ * return (VRVQ_ERR_UNSUPPORTED etc.; out is then left alone). kind: vrvq_conv1d / _ws,
+ * vrvq_conv1d_proj (stride 1), vrvq_conv_transpose1d_pad (k = 2 stride, dil 1); cout_pad is
+ * taken as the packers give it (cout rounded up to 128; the ConvTranspose's cout * stride rows
+ * to 128, or to 192 where the stride does not divide 128), has_x3 = w_x3 != NULL,
+ * has_workspace = a workspace of vrvq_conv1d_workspace bytes, alpha = NULL.
+ * out = the five vrvq_conv_last_launch fields, then path (0: an MFMA tile; 1: the small-Cout
+ * kernels, 2: the Cin = 1 stream kernel, which leave the tile fields 0 and make no
+ * vrvq_conv_last_launch record) and WM (wave rows of the tile). */
+enum vrvq_plan_kind_t { VRVQ_PLAN_CONV = 0, VRVQ_PLAN_PROJ = 1, VRVQ_PLAN_CONV_TRANSPOSE = 2 };
+int vrvq_conv_plan(int kind, int batch, int cin, int tin, int cout, int k, int stride, int pad,
+                   int dil, int has_x3, int has_workspace, int out[7]);
+
 /* Pack a folded Conv1d weight w[Cout][Cin][k] into [Cin][k][cout_pad]. */
 int vrvq_pack_conv1d_weight(const float* w, int cout, int cin, int k, int cout_pad,
                             float* w_packed, vrvq_stream_t stream);

@@ -1,5 +1,5 @@
 """The reference inference driver's own shape (scripts/inference.py:58-70, 88-112): ONE 10-s clip
-(L = 441,000 samples, T = 862 frames: the frame-major fused RVQ with 54 chain parts per clip),
+(L = 441,000 samples, T = 862 frames: the fused RVQ launch with 54 chain parts per clip),
 encoded once and swept over the driver's 12 levels. Needs an MI355X.
 
 Bars (TOL = 1e-4 relative for floats, as in test_gpu_parity.py): codes bit-exact, imp_map / latents /

@@ -4,7 +4,6 @@ plain PyTorch fp32 reference of each conv kernel. Needs an MI355X.
 Bar (north_star): integer codes and masks bit-exact; z_q / latents / waveform within 1e-4
 relative (max-abs normalised)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -1010,10 +1009,9 @@ def test_residual_unit_fused_vs_two_launch(C, T, dil, want_raw):
     # the fused kernel's 4: a different fp32 summation order, compared at 1e-6.
     # With the x3 path on, both forms run the k7 and k1 GEMMs on the split bf16 MFMA in the
     # same K order for C = 64 / 96 / 128 / 192 (bit-identical; C = 128 runs its phase 2 in two
-    # K-halves, VRVQ_RU_P2H=0: fp32 phase 2) and C = 256 an fp32 fused kernel: same sums,
-    # another rounding, compared at 1e-6.
+    # K-halves) and C = 256 an fp32 fused kernel: same sums, another rounding, compared at 1e-6.
     if ops.X3:
-        close = C not in (64, 96, 128, 192) or (C == 128 and os.environ.get("VRVQ_RU_P2H") == "0")
+        close = C not in (64, 96, 128, 192)
     else:
         close = C > 192 or (C == 192 and T <= 96)
     if close:

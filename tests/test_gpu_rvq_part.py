@@ -430,11 +430,12 @@ def test_rvq_stress_fixtures_on_default_path(manifest, name):
 
 
 # ------------------------------------------------------------------ projection epilogue, every tile
-# name, cin, B, T, mode, the launch {BM, BN, KS, x3, S} (conv.hip dispatch_tiles: T <= 96 runs
-# 32-wide tiles, 96-wide from 384 workgroups = B 48; T = 130 64-wide, T = 97 128-wide; k3 runs
-# plain x3 chunks; Cin = 128 has too few K chunks to split, the deep layer splits in 4 when it
-# has a workspace). mode: "op" the torch op (always offers the workspace), "nows" the C-ABI with
-# workspace = NULL, "fp32" the fp32-input loop (no w_x3).
+# name, cin, B, T, mode, the launch {BM, BN, KS, x3, S} (conv.hip tile_width / dispatch_tiles:
+# T <= 96 runs 32-wide tiles, 96-wide from 384 workgroups = B 48; T = 130 64-wide, T = 97
+# 128-wide; k3 runs plain x3 chunks; Cin = 128 has too few K chunks to split, the deep layer
+# splits in 4 when it has a workspace). mode: "op" the torch op (always offers the workspace),
+# "nows" the C-ABI with workspace = NULL, "fp32" the fp32-input loop (no w_x3).
+# tests/test_conv_plan.py checks the same tuples on the host (vrvq_conv_plan).
 PROJ_TILE_CASES = [
     ("x3-32", 128, 3, 87, "op", (128, 32, 3, 1, 0)),
     ("x3-96", 128, 48, 87, "op", (128, 96, 3, 1, 0)),

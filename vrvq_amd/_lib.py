@@ -99,7 +99,8 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_sync_error": ([_P, _P], _I), "vrvq_rvq_timing": ([_I], _I),
          "vrvq_rvq_timing_read": ([_P, _P], _I), "vrvq_rvq_pending_error": ([_P], _I),
          "vrvq_rvq_debug": ([ctypes.c_uint, ctypes.c_uint], _I),
-         "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I)}
+         "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I),
+         "vrvq_conv_plan": ([_I] * 11 + [_P], _I)}
 
 METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
 SPECTRAL_TILE_SAMPLES = 8192  # VRVQ_SPECTRAL_TILE_SAMPLES (tests/test_spectral.py compares)
@@ -197,6 +198,23 @@ def conv_last_launch() -> dict:
     out = (ctypes.c_int * 5)()
     call("vrvq_conv_last_launch", out)
     return dict(zip(("BM", "BN", "KS", "x3", "S"), (int(v) for v in out)))
+
+
+PLAN_KINDS = {"conv": 0, "proj": 1, "convt": 2}  # vrvq_plan_kind_t
+
+
+def conv_plan(kind, batch: int, cin: int, tin: int, cout: int, k: int, stride: int = 1,
+              pad: int = 0, dil: int = 1, x3: bool = True, workspace: bool = True) -> dict:
+    """What a conv call of this shape would launch, decided on the host by the code that
+    launches it (include/vrvq.h vrvq_conv_plan; no GPU needed). kind: "conv" (vrvq_conv1d /
+    _ws), "proj" (vrvq_conv1d_proj) or "convt" (vrvq_conv_transpose1d_pad, k = 2 stride). Returns
+    conv_last_launch()'s keys plus path (0: an MFMA tile, 1: small-Cout kernel, 2: Cin = 1
+    stream kernel; the tile keys are 0 off the MFMA tiles) and WM; raises RuntimeError with the
+    status the launch would return."""
+    out = (ctypes.c_int * 7)()
+    call("vrvq_conv_plan", PLAN_KINDS.get(kind, kind), batch, cin, tin, cout, k, stride, pad, dil,
+         1 if x3 else 0, 1 if workspace else 0, out)
+    return dict(zip(("BM", "BN", "KS", "x3", "S", "path", "WM"), (int(v) for v in out)))
 
 
 def rvq_timing(on: bool) -> bool:

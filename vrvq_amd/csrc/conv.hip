@@ -17,7 +17,6 @@
 #include "common.h"
 #include "conv_core.h"
 #include "conv_x3.h"
-#include <stdlib.h>
 #include <atomic>
 
 namespace {
@@ -25,7 +24,7 @@ namespace {
 using namespace vrvq_conv;
 
 template <int BM, int BN, int WM, int NW, int KS, bool X3, bool PH = false,
-          bool PAIR = x3_pair<KS, BM, BN>(), bool SPLIT = false, bool XPF = false>
+          bool PAIR = x3_pair<KS, BM, BN>(), bool SPLIT = false>
 __global__ __launch_bounds__(64 * NW)
 __attribute__((amdgpu_waves_per_eu(X3 && x3_stages<BM, BN>() == 1 ? 2 : 1)))
 void conv_mfma_kernel(ConvArgs a) {
@@ -52,6 +51,9 @@ void conv_mfma_kernel(ConvArgs a) {
     for (int j = 0; j < TC::RN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  // The 64 x 256 pair k7 tile prefetches the next chunk's x window into registers during the
+  // MFMAs (conv_x3.h XPF; profiles/r06x_xpf_layers.txt: 1-3.5 % per layer).
+  constexpr bool XPF = X3 && KS == 7 && PAIR && !SPLIT;
   // single-buffered operand reads (conv_x3.h) on the k1 and 128-wide 2-tap tiles: 2-6 % per
   // k1 layer, +1.7 % end to end with the ResidualUnit rule (profiles/r04q_sb_ab.txt)
 #ifdef VRVQ_X3_SB_ALL  // A/B build
@@ -66,7 +68,7 @@ void conv_mfma_kernel(ConvArgs a) {
       // 64 NW threads x RM RN 16 floats, lane-contiguous: 256-B stores), no epilogue here
       constexpr int CK = X3Cfg<KS, PAIR>::CK;
       const int nch = (a.cin + CK - 1) / CK, per = (nch + a.ks_split - 1) / a.ks_split;
-      if (ks * per < nch)  // (a forced part count can leave the last part empty: zero sums)
+      if (ks * per < nch)  // (an empty part would store zero sums; splitk_parts makes none)
         conv_mainloop_x3<BM, BN, WM, NW, KS, PH, PAIR, SB>(a, smem, acc, b, m0, n0, ks * per,
                                                             min(nch, (ks + 1) * per));
       constexpr int NR = TC::RM * TC::RN * 16;
@@ -369,28 +371,79 @@ __global__ __launch_bounds__(256) void conv_cin1_stream_kernel(ConvArgs a) {
   }
 }
 
-int launch_small(const ConvArgs& a, int batch, int ks, hipStream_t st) {
+// What runs for a conv shape. The functions below decide it and launch it in one pass; called
+// with a ConvPlan* they stop once the plan is known, before hipFuncSetAttribute and the launch
+// (vrvq_conv_plan: the same code and the same status, no device touched).
+enum ConvPath { PATH_MFMA = 0, PATH_SMALL_COUT = 1, PATH_CIN1 = 2 };
+struct ConvPlan {
+  int path;        // ConvPath
+  int BM, BN, WM;  // MFMA tile and its wave rows (0 off the MFMA tiles)
+  int KS;          // the GEMM's taps (2: the phase-split view, the polyphase ConvTranspose)
+  int x3;          // 0 fp32-input loop | 1 x3 on plain K chunks | 2 x3 on pair chunks
+  int S;           // split-K parts (0: unsplit)
+};
+
+// Tile and path of the last MFMA conv launch (vrvq_conv_last_launch, a host-side debug query:
+// the tests assert the path they claim to pin). One word, so concurrent callers never read a
+// torn record: BM (9 bits) | BN << 9 (9) | KS << 18 (5) | x3 << 23 (2) | S << 25 (7).
+std::atomic<unsigned> g_last_launch{0};
+
+void note_launch(const ConvPlan& p) {
+  g_last_launch.store((unsigned)p.BM | (unsigned)p.BN << 9 | (unsigned)p.KS << 18 |
+                      (unsigned)p.x3 << 23 | (unsigned)(p.S & 127) << 25,
+                      std::memory_order_relaxed);
+}
+
+// The exit of every MFMA decision: a plan-only call (plan != null, its launches were dry) hands
+// the plan back, a launch records it.
+int finish(int rc, const ConvPlan& p, ConvPlan* plan) {
+  if (rc == 0) {
+    if (plan) *plan = p;
+    else note_launch(p);
+  }
+  return rc;
+}
+
+// One conv kernel: its dynamic-LDS limit raised where it needs more than 64 KiB, then the
+// launch. dry (a plan-only call): neither.
+int launch_kernel(void (*kernel)(ConvArgs), long long nblk, int threads, size_t lds,
+                  hipStream_t st, const ConvArgs& a, bool dry) {
+  if (dry) return 0;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  ConvArgs arg = a;
+  void* params[] = {&arg};
+  hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3((unsigned)nblk),
+                                 dim3(threads), params, lds, st);
+  return e != hipSuccess ? (int)e : vrvq_launch_status();
+}
+
+int launch_small(const ConvArgs& a, int batch, int ks, hipStream_t st, ConvPlan* plan) {
+  const ConvPlan p{PATH_SMALL_COUT, 0, 0, 0, ks, 0, 0};
   if (a.M == 1 && a.cout == 1 && a.stride == 1 && a.dil == 1 && a.tin % 4 == 0 &&
       ((ks == 7 && a.pad == 3) || (ks == 3 && a.pad == 1))) {
     const long long nblk = (long long)batch * ((a.ng + 256 * C1_T - 1) / (256 * C1_T));
     if (nblk <= 0 || nblk > 0x7fffffffLL) return VRVQ_ERR_ARG;
+    if (plan) *plan = p;
     // the consumer-side Snake variant is its own kernel: its registers do not set the plain
     // variant's occupancy
-    if (ks == 7 && a.alpha)
-      hipLaunchKernelGGL((conv_cout1_stream_kernel<7, 3, true>), dim3((unsigned)nblk), dim3(256), 0, st, a);
-    else if (ks == 7)
-      hipLaunchKernelGGL((conv_cout1_stream_kernel<7, 3, false>), dim3((unsigned)nblk), dim3(256), 0, st, a);
-    else if (a.alpha)
-      hipLaunchKernelGGL((conv_cout1_stream_kernel<3, 1, true>), dim3((unsigned)nblk), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((conv_cout1_stream_kernel<3, 1, false>), dim3((unsigned)nblk), dim3(256), 0, st, a);
-    return vrvq_launch_status();
+    void (*kernel)(ConvArgs) =
+        ks == 7 ? (a.alpha ? conv_cout1_stream_kernel<7, 3, true> : conv_cout1_stream_kernel<7, 3, false>)
+                : (a.alpha ? conv_cout1_stream_kernel<3, 1, true> : conv_cout1_stream_kernel<3, 1, false>);
+    return launch_kernel(kernel, nblk, 256, 0, st, a, plan != nullptr);
   }
   if (a.cin * ks * (a.M == 1 ? 1 : SMALL_COUT) > SMALL_WMAX) return VRVQ_ERR_UNSUPPORTED;
   const size_t lds = (size_t)(SMALL_WMAX + SMALL_SC * (SMALL_BT + (ks - 1) * a.dil)) * sizeof(float);
   if (lds > 64 * 1024) return VRVQ_ERR_UNSUPPORTED;
   const long long nblk = (long long)batch * ((a.ng + SMALL_BT - 1) / SMALL_BT);
   if (nblk <= 0 || nblk > 0x7fffffffLL) return VRVQ_ERR_ARG;
+  if (plan) {
+    *plan = p;
+    return 0;
+  }
   if (a.M == 1)
     hipLaunchKernelGGL(conv_small_cout_kernel<1>, dim3((unsigned)nblk), dim3(256), lds, st, a, ks);
   else
@@ -398,87 +451,35 @@ int launch_small(const ConvArgs& a, int batch, int ks, hipStream_t st) {
   return vrvq_launch_status();
 }
 
-// x3 ConvTranspose with M a multiple of 96 (not of 128): 96-row pair tiles (default) |
-// VRVQ_CONV_CONVT96=0: the 192 x 128 two-stage tile
-static int convt_96() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_CONVT96");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-// The 64 x 256 pair k7 tiles with the next chunk's x window prefetched into registers during the
-// MFMAs (conv_x3.h XPF; profiles/r06x_xpf_layers.txt: 1-3.5 % per layer). Tuning override
-// VRVQ_CONV_XPF=0 | 1.
-static int conv_x3_xpf() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_XPF");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-// Cin = 1 convs on conv_cin1_stream_kernel (default) | VRVQ_CONV_CIN1=0: the fp32 MFMA tile
-static int cin1_stream() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_CIN1");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-
-
 // The x3 launch of a tile (PAIR: its K-chunk form); VRVQ_ERR_UNSUPPORTED when its LDS does not
 // fit (the caller then takes the fp32-input loop).
-template <int BM, int BN, int WM, int NW, int KS, bool PAIR, bool SPLIT = false, bool XPF = false>
-int launch_x3(const ConvArgs& a, int XW, size_t epi, long long nblk, hipStream_t st) {
+template <int BM, int BN, int WM, int NW, int KS, bool PAIR, bool SPLIT = false>
+int launch_x3(const ConvArgs& a, int XW, size_t epi, long long nblk, hipStream_t st, bool dry) {
   // the pair tiles' Snake table only when the staging applies a Snake (the producer-side
   // snake(x) inputs of the k7 layers need none: 3-6 KB of LDS back)
   size_t lx = x3_lds_bytes<KS, BM, BN, PAIR>(XW, a.alpha ? (a.psh ? a.cin >> a.psh : a.cin) : 0);
   if (lx < epi) lx = epi;
   if (lx > 160 * 1024) return VRVQ_ERR_UNSUPPORTED;
-  if constexpr (KS == 2) {
-    if (a.psh) {  // strided conv through the phase-split view
-      if (lx > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(
-            (const void*)conv_mfma_kernel<BM, BN, WM, NW, KS, true, true, PAIR, SPLIT, XPF>,
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lx);
-        if (e != hipSuccess) return (int)e;
-      }
-      hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, NW, KS, true, true, PAIR, SPLIT, XPF>),
-                         dim3((unsigned)nblk), dim3(64 * NW), lx, st, a);
-      return vrvq_launch_status();
-    }
+  // A strided conv through the phase-split view: dispatch_tiles gives it a 2-tap pair tile (32-
+  // or 128-wide, on plain chunks where the view's Cin is no multiple of 32) or the split-K tile,
+  // which takes nothing else among the 2-tap GEMMs.
+  constexpr bool PH_TILE = KS == 2 && (x3_pair<KS, BM, BN>() || SPLIT);
+  if constexpr (PH_TILE) {
+    if (a.psh)
+      return launch_kernel(conv_mfma_kernel<BM, BN, WM, NW, KS, true, true, PAIR, SPLIT>, nblk,
+                           64 * NW, lx, st, a, dry);
   }
-  if (a.psh) return VRVQ_ERR_ARG;
-  if (lx > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(
-        (const void*)conv_mfma_kernel<BM, BN, WM, NW, KS, true, false, PAIR, SPLIT, XPF>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lx);
-    if (e != hipSuccess) return (int)e;
+  if constexpr (SPLIT && KS == 2) {
+    return VRVQ_ERR_ARG;  // (splitk_parts: the only 2-tap GEMM that splits is the view's)
+  } else {
+    if (a.psh) return VRVQ_ERR_ARG;
+    return launch_kernel(conv_mfma_kernel<BM, BN, WM, NW, KS, true, false, PAIR, SPLIT>, nblk,
+                         64 * NW, lx, st, a, dry);
   }
-  hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, NW, KS, true, false, PAIR, SPLIT, XPF>),
-                     dim3((unsigned)nblk), dim3(64 * NW), lx, st, a);
-  return vrvq_launch_status();
-}
-
-// Tile and path of the last MFMA conv launch (vrvq_conv_last_launch, a host-side debug query:
-// the tests assert the path they claim to pin). One word, so concurrent callers never read a
-// torn record: BM (9 bits) | BN << 9 (9) | KS << 18 (5) | x3 << 23 (2) | S << 25 (7).
-std::atomic<unsigned> g_last_launch{0};
-
-int note_launch(int rc, int bm, int bn, int ks, int x3, int S) {
-  if (rc == 0)
-    g_last_launch.store((unsigned)bm | (unsigned)bn << 9 | (unsigned)ks << 18 |
-                        (unsigned)x3 << 23 | (unsigned)(S & 127) << 25,
-                        std::memory_order_relaxed);
-  return rc;
 }
 
 template <int BM, int BN, int WM, int NW, int KS>
-int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
+int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st, ConvPlan* plan) {
   ConvArgs a = a0;
   a.n_mt = (a.M + BM - 1) / BM;
   a.n_nt = (a.ng + BN - 1) / BN;
@@ -497,24 +498,23 @@ int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
   }
   const long long nblk = (long long)a.n_mt * a.n_nt * batch;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return VRVQ_ERR_ARG;
+  ConvPlan p{PATH_MFMA, BM, BN, WM, KS, 0, 0};
+  const bool dry = plan != nullptr;
   // bf16x3 split path (conv_x3.h): stride-1 windows, a pre-split weight, the stage in LDS
   if constexpr (NW == 4 && BM <= 192 && (KS == 1 || KS == 2 || KS == 3 || KS == 7)) {
     constexpr int XW_MAX = (BN - 1) + (KS - 1) * (KS == 7 ? 9 : 1) + 1;
     if (a.w3 != nullptr && a.stride == 1 && a.ssh == 0 && XW <= XW_MAX) {
       // pair tiles (conv_x3.h) need whole K-chunks: other Cin run the tile on plain chunks
-      int rc = VRVQ_ERR_UNSUPPORTED;
-      int x3 = 1;  // plain chunks | 2: pair chunks
+      int rc;
       if (x3_pair<KS, BM, BN>() && a.cin % X3Cfg<KS, true>::CK == 0) {
-        constexpr bool kXpf = KS == 7 && x3_pair<KS, BM, BN>();  // the 64 x 256 pair k7 tile
-        x3 = 2;
-        if (kXpf && conv_x3_xpf())
-          rc = launch_x3<BM, BN, WM, NW, KS, x3_pair<KS, BM, BN>(), false, kXpf>(a, XW, epi, nblk, st);
-        else
-          rc = launch_x3<BM, BN, WM, NW, KS, x3_pair<KS, BM, BN>()>(a, XW, epi, nblk, st);
+        p.x3 = 2;
+        rc = launch_x3<BM, BN, WM, NW, KS, x3_pair<KS, BM, BN>()>(a, XW, epi, nblk, st, dry);
+      } else {
+        p.x3 = 1;
+        rc = launch_x3<BM, BN, WM, NW, KS, false>(a, XW, epi, nblk, st, dry);
       }
-      else
-        rc = launch_x3<BM, BN, WM, NW, KS, false>(a, XW, epi, nblk, st);
-      if (rc != VRVQ_ERR_UNSUPPORTED) return note_launch(rc, BM, BN, KS, x3, 0);
+      if (rc != VRVQ_ERR_UNSUPPORTED) return finish(rc, p, plan);
+      p.x3 = 0;  // the stage does not fit in LDS: the fp32-input loop
     }
   }
   if (a.psh) return VRVQ_ERR_UNSUPPORTED;  // the phase-split view exists on the x3 loop only
@@ -522,106 +522,8 @@ int launch_cfg(const ConvArgs& a0, int batch, hipStream_t st) {
   size_t lds = 2 * (size_t)(CK * KS * BM + CK * XWP) * sizeof(float);
   if (lds < epi) lds = epi;  // epilogue tile
   if (lds > 160 * 1024) return VRVQ_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_mfma_kernel<BM, BN, WM, NW, KS, false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, WM, NW, KS, false>), dim3((unsigned)nblk),
-                     dim3(64 * NW), lds, st, a);
-  return note_launch(vrvq_launch_status(), BM, BN, KS, 0, 0);
-}
-
-
-
-// Measured (profiles/r01j_conv_k1_ab.txt): 768 x 768 k1 + skip at T = 696, 485 -> 386 us with
-// 192-row tiles (384: 930 -> 922 us); 256-row tiles for 512 / 768 were slower (248 / 473 us).
-static int conv_k1_192() {  // tuning override: VRVQ_CONV_K1_192=0 (128-row) | 1 (192-row, default)
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_K1_192");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-// Measured (profiles/r01j_conv_k7_ab.txt): 768 x 768 k7 at T = 696, 2150 -> 1795 us with
-// 192-row x 64-col tiles (K chunk 4 channels), 427 -> 434 audio-sec/s end to end.
-static int conv_k7_192() {  // tuning override: VRVQ_CONV_K7_192=0 | 1 (192-row k7 tiles at BN 64,
-  static const int v = [] {  // default) | 2 (also at BN 128)
-    const char* e = getenv("VRVQ_CONV_K7_192");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-// Measured (profiles/r01k_convt_ab.txt): ConvT 768->384 s8 2443 -> 2345 us, 384->192 s4
-// 2887 -> 2660 us with 192-row tiles; 432 -> 434 audio-sec/s.
-static int conv_t_192() {  // tuning override: VRVQ_CONVT_192=0 | 1 (192-row ConvT tiles, default)
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONVT_192");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
-
-// T = 87 layers: the 96-wide tile (one per clip) when it gives at least this many workgroups,
-// else three 32-wide tiles (tuning override VRVQ_CONV_BN96_MIN; each N tile re-streams its M
-// tile's whole weight block, so the narrow tiles triple the weight traffic)
-static long long conv_bn96_min() {
-  static const long long v = [] {
-    const char* e = getenv("VRVQ_CONV_BN96_MIN");
-    return e ? atoll(e) : 384LL;
-  }();
-  return v;
-}
-
-// The phase-split strided convs at T <= 96 (512 -> 1024 s8 at T = 87): tile width, fixed per
-// layer type (batch-invariant sums). Tuning override VRVQ_CONV_PH_T87=32 (default) | 96.
-// Measured (profiles/r05zf_t87_tiles_ab.txt): 96-wide 691 -> 629 us for that layer, bench
-// within the spread; the k3 layers at 96 (VRVQ_CONV_BN96_MIN=0) no faster. The layer is bound
-// by its 128-chunk serial K loop per workgroup, not by the weight re-streaming alone.
-static int conv_ph_t87() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_PH_T87");
-    return e && atoi(e) == 96 ? 96 : 32;
-  }();
-  return v;
-}
-
-// x3 k7 layers over long rows (M a multiple of 64 and >= 128, Cin a multiple of 16): 64 x 256
-// tiles on 16-channel "pair" K-chunks (conv_x3.h: no zero octet, 168 MFMAs per wave between
-// barriers). 384 x 384 k7 at T = 5568, B = 32: 2027 -> 755-796 us (0.43 -> 0.50 of the x3
-// ceiling), 256 x 256: 934 -> 781-785 us (profiles/r03_x3_pair_ab.txt).
-// 768 x 768 / 512 x 512 k7 at T = 696: 1125 -> 962 / 514 -> 407 us despite 72 of every 768
-// columns padded. Tuning override VRVQ_CONV_X3_WIDE=0 (128- / 192-row tiles, 8-channel
-// chunks) | 1 (pair tiles for T >= 4096) | 2 (pair tiles for T >= 640, default).
-static int conv_x3_wide() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_X3_WIDE");
-    return e ? atoi(e) : 2;
-  }();
-  return v;
-}
-
-// 2-tap GEMMs at T < 4096 that the padding rule sends to 64-wide tiles run 128-wide pair tiles
-// (half the weight re-streaming, 32-channel K chunks): 256 -> 512 s8 at T = 696 940 -> 878 us,
-// ConvT 768 -> 384 s8 1388 -> 1296 us (profiles/r04ze_ph128_ab.txt). Tuning override
-// VRVQ_CONV_PH128=1 (the strided encoder convs only) | 0 (64-wide) | 2 (default: also the
-// ConvTranspose layers)
-static int conv_ph128() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_PH128");
-    return e ? atoi(e) : 2;
-  }();
-  return v;
-}
-
-static int conv_k1x3_192() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_K1X3_192");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
+  return finish(launch_kernel(conv_mfma_kernel<BM, BN, WM, NW, KS, false>, nblk, 64 * NW, lds, st,
+                              a, dry), p, plan);
 }
 
 // Split-K for the deep-K, narrow-N layers at T <= 96 (the encoder's 512 -> 1024 s8 conv, the
@@ -629,34 +531,26 @@ static int conv_k1x3_192() {
 // re-streamed every M tile's whole weight block per 32 columns (50 MB of planes x 87 column
 // tiles for the s8 conv), and one 96-wide tile per clip gives too few workgroups to hide a
 // 128-chunk serial K loop. Here: 128 x 96 tiles (one per clip: the weight block read once per
-// clip) with the channel chunks cut into S = 4 parts (at least 8 chunks a part) -- a function of
-// the layer only, so a clip's sums do not change with the batch. Per layer at B = 32
-// (profiles/r06ks_splitk_sweep.txt, S = none / 2 / 3 / 4 / 6 / 8): 512 -> 1024 s8 645 / 441 /
-// 469 / 445 / 462 / 455 us, 1024 -> 1024 k3 182 / 140 / 169 / 143 / 155 / 159, 1024 -> 512 k3
-// 124 / 95 / 91 / 79 / 94 / 85, 512 -> 128 k3 48 -> 38 (S <= 4: 32 chunks), 1024 -> 1536 k7
-// 518 / 525 / 530 / 467 / 496 / 479: S = 4 is within 1 % of the best everywhere.
-// Tuning override VRVQ_CONV_SPLITK=0 (off) | S (forced part count).
-static int conv_splitk_env() {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_CONV_SPLITK");
-    return e ? atoi(e) : -1;
-  }();
-  return v;
-}
+// clip) with the channel chunks cut into SPLITK_PARTS parts of at least SPLITK_MIN_CHUNKS
+// chunks -- a function of the layer only, so a clip's sums do not change with the batch. Per
+// layer at B = 32 (profiles/r06ks_splitk_sweep.txt, S = none / 2 / 3 / 4 / 6 / 8): 512 -> 1024 s8
+// 645 / 441 / 469 / 445 / 462 / 455 us, 1024 -> 1024 k3 182 / 140 / 169 / 143 / 155 / 159,
+// 1024 -> 512 k3 124 / 95 / 91 / 79 / 94 / 85, 512 -> 128 k3 48 -> 38 (S <= 4: 32 chunks),
+// 1024 -> 1536 k7 518 / 525 / 530 / 467 / 496 / 479: S = 4 is within 1 % of the best everywhere.
+constexpr int SPLITK_PARTS = 4;
+constexpr int SPLITK_MIN_CHUNKS = 8;
 
 // K parts of a layer (0: none). ks = the GEMM's taps (2 for the phase-split view), cin = the
 // GEMM's channels (the view's for a strided conv). The same for vrvq_conv1d_proj (the encoder's
 // last conv, whose shape the ImportanceSubnet's first conv shares): its projection epilogue then
 // runs in the split-K epilogue launch, on the same z bits as the plain conv's.
 int splitk_parts(int M, int cin, int ng, int ks, bool psh, bool up, bool x3) {
-  const int env = conv_splitk_env();
-  if (env == 0 || !x3 || up || ng > 96 || M % 128 != 0) return 0;
+  if (!x3 || up || ng > 96 || M % 128 != 0) return 0;
   if (!(ks == 3 || ks == 7 || (ks == 2 && psh))) return 0;
   const int ck = ks == 2 ? X3Cfg<2, true>::CK : ks == 3 ? X3Cfg<3>::CK : X3Cfg<7>::CK;
   if (ks == 2 && cin % ck != 0) return 0;
   const int nch = (cin + ck - 1) / ck;
-  int S = env > 0 ? env : 4;
-  if (S > nch / 8) S = nch / 8;
+  const int S = nch / SPLITK_MIN_CHUNKS < SPLITK_PARTS ? nch / SPLITK_MIN_CHUNKS : SPLITK_PARTS;
   return S >= 2 ? S : 0;
 }
 
@@ -665,13 +559,13 @@ size_t splitk_bytes(int S, int M, int ng, int batch) {
 }
 
 template <int KS>
-int launch_splitk(const ConvArgs& a0, int batch, int S, hipStream_t st) {
+int launch_splitk(const ConvArgs& a0, int batch, int S, hipStream_t st, ConvPlan* plan) {
   if constexpr (KS == 2 || KS == 3 || KS == 7) {
     ConvArgs a = a0;
     a.ks_split = S;
     a.n_mt = a.M / 128;
     a.n_nt = (a.ng + 95) / 96;
-      if (a.m_pad < a.n_mt * 128) return VRVQ_ERR_ARG;
+    if (a.m_pad < a.n_mt * 128) return VRVQ_ERR_ARG;
     const int XW = 95 + (KS - 1) * a.dil + 1;
     constexpr int XW_MAX = 95 + (KS - 1) * (KS == 7 ? 9 : 1) + 1;
     if (XW > XW_MAX) return VRVQ_ERR_UNSUPPORTED;
@@ -679,126 +573,142 @@ int launch_splitk(const ConvArgs& a0, int batch, int S, hipStream_t st) {
     if (a.pj_part && epi < (size_t)PJE_LDS) epi = PJE_LDS;
     const long long tiles = (long long)a.n_mt * a.n_nt * batch;
     if (tiles * S > 0x7fffffffLL) return VRVQ_ERR_ARG;
-    const int rc = launch_x3<128, 96, 4, 4, KS, KS == 2, true>(a, XW, epi, tiles * S, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv_splitk_epilogue_kernel<128, 96, 4, 4>), dim3((unsigned)tiles),
-                       dim3(256), epi, st, a);
-    return note_launch(vrvq_launch_status(), 128, 96, KS, KS == 2 ? 2 : 1, S);
+    const ConvPlan p{PATH_MFMA, 128, 96, 4, KS, KS == 2 ? 2 : 1, S};
+    const bool dry = plan != nullptr;
+    int rc = launch_x3<128, 96, 4, 4, KS, KS == 2, true>(a, XW, epi, tiles * S, st, dry);
+    if (rc == 0)
+      rc = launch_kernel(conv_splitk_epilogue_kernel<128, 96, 4, 4>, tiles, 256, epi, st, a, dry);
+    return finish(rc, p, plan);
   } else {
-    (void)a0; (void)batch; (void)S; (void)st;
+    (void)a0; (void)batch; (void)S; (void)st; (void)plan;
     return VRVQ_ERR_UNSUPPORTED;
   }
 }
 
-// Tile choice: BM from the GEMM row count, BN minimising padded columns (prefer wide).
+// ---- Tile choice (DESIGN.md "Conv tiles" has the same rules as a table) ----
+// (a) Column width BN of the tile for ng GEMM columns.
+//
+// T <= 96 layers: one 96-wide tile per clip when that gives at least this many workgroups (1.5
+// per CU), else three 32-wide tiles: each N tile re-streams its M tile's whole weight block, so
+// the narrow tiles triple the weight traffic, but with fewer 96-wide ones the CUs run short of
+// workgroups to hide each one's serial K loop (profiles/r02zl_x3_sq_counters.txt; the k3 / k7
+// layers 96-wide at B = 32 no faster, profiles/r05zf_t87_tiles_ab.txt).
+constexpr long long BN96_MIN_WORKGROUPS = 384;
+
 template <int KS>
-int dispatch_tiles(const ConvArgs& a, int batch, hipStream_t st) {
+int tile_width(const ConvArgs& a, int batch) {
+  const bool x3_2tap = KS == 2 && a.w3 != nullptr;
+  if (a.ng <= 32) return 32;
+  if (a.ng <= 96) {
+    // 2-tap x3 GEMMs: the 32-wide tile pairs its K octets (conv_x3.h x3_pair) and the 96-wide
+    // one does not, so a clip's sums would change order with the batch. Their width is fixed
+    // per layer type instead (batch-invariant outputs, tests/test_gpu_parity.py
+    // test_batch_invariance_*): the polyphase ConvTranspose 96-wide, the others (the phase-split
+    // strided convs: 96-wide 691 -> 629 us for 512 -> 1024 s8, bench within the spread,
+    // profiles/r05zf_t87_tiles_ab.txt) 32-wide.
+    if (x3_2tap) return a.up > 0 ? 96 : 32;
+    return (long long)((a.M + 127) / 128) * batch >= BN96_MIN_WORKGROUPS ? 96 : 32;
+  }
+  // Longer rows: 128-wide, or 64-wide below T = 4096 where that pads markedly fewer columns.
+  // Not for k = 16 (the stride-8 encoder convs on the fp32-input loop): the 8 MB weight block
+  // does not fit in L2, so the 128-wide tile's halved weight re-streaming beats its padding
+  // (1490 -> 1323 us at T = 696, profiles/r02u_conv_ab.txt). Nor for the x3 strided convs and
+  // ConvTransposes, whose 128-wide tile runs 32-channel pair chunks: 256 -> 512 s8 at T = 696
+  // 940 -> 878 us, ConvT 768 -> 384 s8 1388 -> 1296 us (profiles/r04ze_ph128_ab.txt).
+  auto waste = [&](int bn) { return ((a.ng + bn - 1) / bn) * bn - a.ng; };
+  if (a.ng < 4096 && KS != 16 && waste(64) * 10 < waste(128) * 7 &&
+      !(x3_2tap && (a.psh > 0 || a.up > 0)))
+    return 64;
+  return 128;
+}
+
+// x3 k7 layers from this many columns (M a multiple of 64 and >= 128, Cin a multiple of 16) run
+// 64 x 256 tiles on 16-channel "pair" K-chunks (conv_x3.h: no zero octet, 168 MFMAs per wave
+// between barriers). 384 x 384 k7 at T = 5568, B = 32: 2027 -> 755-796 us, 256 x 256: 934 ->
+// 781-785 us; 768 x 768 / 512 x 512 k7 at T = 696: 1125 -> 962 / 514 -> 407 us despite 72 of
+// every 768 columns padded (profiles/r03_x3_pair_ab.txt).
+constexpr int K7_PAIR_MIN_COLUMNS = 640;
+
+// A BM-row tile, 64 columns wide where tile_width chose that, else 128.
+template <int BM, int WM, int KS>
+int launch_bn(int bn, const ConvArgs& a, int batch, hipStream_t st, ConvPlan* plan) {
+  if constexpr (KS != 16) {  // (tile_width: k = 16 never runs 64-wide)
+    if (bn == 64) return launch_cfg<BM, 64, WM, 4, KS>(a, batch, st, plan);
+  }
+  return launch_cfg<BM, 128, WM, 4, KS>(a, batch, st, plan);
+}
+
+// (b) Row tile BM from the GEMM rows M; the first rule that applies.
+template <int KS>
+int dispatch_tiles(const ConvArgs& a, int batch, hipStream_t st, ConvPlan* plan) {
   if (a.ks_part != nullptr) {
     const int S = splitk_parts(a.M, a.cin, a.ng, KS, a.psh > 0, a.up > 0, a.w3 != nullptr);
     if (S > 0) {
-      const int rc = launch_splitk<KS>(a, batch, S, st);
+      const int rc = launch_splitk<KS>(a, batch, S, st, plan);
       if (rc != VRVQ_ERR_UNSUPPORTED) return rc;
     }
   }
-  auto waste = [&](int bn) { return ((a.ng + bn - 1) / bn) * bn - a.ng; };
-  int bn;
-  if (a.ng <= 32) bn = 32;
-  else if (a.ng <= 96) {
-    // T = 87 / 88 layers: one 96-wide tile per clip when that still gives >= 1.5 workgroups
-    // per CU, otherwise three 32-wide tiles (more workgroups for the deep-K, narrow-N GEMMs).
-    const long long blocks96 = (long long)((a.M + 127) / 128) * batch;
-    bn = blocks96 >= conv_bn96_min() ? 96 : 32;
-    // 2-tap x3 GEMMs: the 32-wide tile pairs its K octets (conv_x3.h x3_pair) and the 96-wide
-    // one does not, so a clip's sums would change order with the batch. Their width is fixed
-    // instead (batch-invariant outputs, tests/test_gpu_parity.py test_batch_invariance_*): the
-    // polyphase ConvTranspose (up > 0) 96-wide, the phase-split strided convs 32-wide -- what
-    // configs[1] (B = 32) ran before.
-    if (KS == 2 && a.w3 != nullptr) bn = a.up > 0 ? 96 : conv_ph_t87();
+  const int bn = tile_width<KS>(a, batch);
+  const bool x3 = a.w3 != nullptr;
+  if constexpr (KS == 2) {
+    // Polyphase ConvTranspose1d with a stride that does not divide 128 (3, 6): 192-row tiles,
+    // which hold whole output channels, 64-wide up to T = 96 (other strides, 5, 7, ..., are
+    // rejected by launch_cfg).
+    if (a.up > 0 && 128 % a.up != 0) return launch_bn<192, 2, KS>(bn <= 96 ? 64 : bn, a, batch, st, plan);
   }
-  // k = 16 (the stride-8 encoder convs): the 8 MB weight block does not fit in L2, so the
-  // 128-wide tile's halved weight re-streaming beats its padding (1490 -> 1323 us at T = 696,
-  // profiles/r02u_conv_ab.txt)
-  else if (a.ng < 4096 && KS != 16 && waste(64) * 10 < waste(128) * 7)
-    bn = 64;
-  else bn = 128;
-  if (KS == 2 && bn == 64 && a.w3 != nullptr &&
-      ((a.psh > 0 && conv_ph128() >= 1) || (a.up > 0 && conv_ph128() >= 2)))
-    bn = 128;
-  if (KS == 2 && a.up > 0 && 128 % a.up != 0) {
-    // polyphase ConvTranspose1d with a stride that does not divide 128 (3, 6): 192-row tiles,
-    // which hold whole output channels; other strides (5, 7, ...) are rejected by launch_cfg
-    if (bn <= 96 && bn != 64) bn = 64;
-    if (bn == 64) return launch_cfg<192, 64, 2, 4, KS>(a, batch, st);
-    return launch_cfg<192, 128, 2, 4, KS>(a, batch, st);
-  }
-  if (a.M <= 32) return launch_cfg<32, 128, 1, 4, KS>(a, batch, st);
+  if (a.M <= 32) return launch_cfg<32, 128, 1, 4, KS>(a, batch, st, plan);
   if constexpr (KS == 7) {
-    const int wide = conv_x3_wide();
-    if (a.w3 != nullptr && a.stride == 1 && a.up == 0 && a.M >= 128 && a.M % 64 == 0 &&
-        a.cin % 16 == 0 && ((wide >= 1 && a.ng >= 4096) || (wide == 2 && a.ng >= 640))) {
-      return launch_cfg<64, 256, 1, 4, KS>(a, batch, st);
-    }
+    if (x3 && a.M >= 128 && a.M % 64 == 0 && a.cin % 16 == 0 && a.ng >= K7_PAIR_MIN_COLUMNS)
+      return launch_cfg<64, 256, 1, 4, KS>(a, batch, st, plan);
   }
-  if (bn == 32) return launch_cfg<128, 32, 4, 4, KS>(a, batch, st);
-  if (bn == 96) return launch_cfg<128, 96, 4, 4, KS>(a, batch, st);
-  if (a.M <= 64) {
-    if (bn == 64) return launch_cfg<64, 64, 2, 4, KS>(a, batch, st);
-    return launch_cfg<64, 128, 2, 4, KS>(a, batch, st);
-  }
+  // T <= 96: 128 rows at the width chosen above
+  if (bn == 32) return launch_cfg<128, 32, 4, 4, KS>(a, batch, st, plan);
+  if (bn == 96) return launch_cfg<128, 96, 4, 4, KS>(a, batch, st, plan);
+  if (a.M <= 64) return launch_bn<64, 2, KS>(bn, a, batch, st, plan);
   // 96- and 192-row tiles: no padded rows for the C = 96 / 192 decoder blocks
-  if (a.M <= 96) {
-    return launch_cfg<96, 128, 1, 4, KS>(a, batch, st);
+  if (a.M <= 96) return launch_cfg<96, 128, 1, 4, KS>(a, batch, st, plan);
+  if constexpr (KS == 7) {
+    // 768 x 768 k7 at T = 696: 2150 -> 1795 us with 192-row x 64-col tiles (K chunk 4 channels),
+    // 427 -> 434 audio-sec/s end to end (profiles/r01j_conv_k7_ab.txt)
+    if (a.M % 192 == 0 && bn == 64) return launch_cfg<192, 64, 2, 4, KS>(a, batch, st, plan);
   }
-  if (KS == 7 && conv_k7_192() && a.M % 192 == 0) {
-    if (bn == 64) return launch_cfg<192, 64, 2, 4, KS>(a, batch, st);
-    if (conv_k7_192() == 2) return launch_cfg<192, 128, 2, 4, KS>(a, batch, st);
+  if constexpr (KS == 2) {
+    // Polyphase ConvTranspose1d, M = Cout * stride phase rows. fp32-input loop, M a multiple of
+    // 192: 192-row tiles (ConvT 768 -> 384 s8 2443 -> 2345 us, 384 -> 192 s4 2887 -> 2660 us,
+    // profiles/r01k_convt_ab.txt); with the x3 weights the 128-row tiles, two workgroups per CU,
+    // are faster (638 -> 649 audio-sec/s at B = 32, profiles/r02zh_tile_ab.txt) ...
+    if (a.up > 0 && !x3 && a.M % 192 == 0) return launch_bn<192, 2, KS>(bn, a, batch, st, plan);
+    // ... except M a multiple of 96 and not of 128 (192 -> 96 s2: M = 192): 96-row tiles on the
+    // pair chunks, two workgroups per CU, instead of the two-stage 192 x 128 tile (981-988 vs
+    // 942-954 us, profiles/r06t_convt_layers.txt)
+    if (a.up > 0 && x3 && a.M % 96 == 0 && a.M % 128 != 0)
+      return launch_cfg<96, 128, 1, 4, KS>(a, batch, st, plan);
   }
-  // (the 192-row k1 / ConvT tiles are fp32-path choices: with the x3 weights the 128-row
-  // tiles, two workgroups per CU, are faster — 638 -> 649 audio-sec/s at B = 32,
-  // profiles/r02zh_tile_ab.txt)
-  if (KS == 2 && a.up > 0 && conv_t_192() && a.w3 == nullptr && a.M % 192 == 0) {
-    // polyphase ConvTranspose1d with M = Cout * stride phase rows a multiple of 192
-    if (bn == 64) return launch_cfg<192, 64, 2, 4, KS>(a, batch, st);
-    return launch_cfg<192, 128, 2, 4, KS>(a, batch, st);
-  }
-  if (KS == 2 && a.up > 0 && a.w3 != nullptr && a.M % 96 == 0 && a.M % 128 != 0 &&
-      convt_96()) {
-    // x3 polyphase ConvTranspose1d with 96-row multiples (192 -> 96 s2: M = 192): 96-row
-    // tiles on the pair chunks (two workgroups per CU) instead of the two-stage 192 x 128 tile
-    // (single-stage 192 x 64 tiles, x read once: 981-988 vs 942-954 us, r06t_convt_layers.txt)
-    return launch_cfg<96, 128, 1, 4, KS>(a, batch, st);
-  }
-  if ((KS >= 3 || (KS == 2 && a.up > 0)) && a.M % 128 != 0 && a.M % 192 == 0) {
-    // (KS == 2 with up > 0: the polyphase ConvTranspose1d 192->96 s2, M = 192 phase rows)
-    return launch_cfg<192, 128, 2, 4, KS>(a, batch, st);
+  if constexpr (KS >= 3) {
+    if (a.M % 128 != 0 && a.M % 192 == 0) return launch_cfg<192, 128, 2, 4, KS>(a, batch, st, plan);
   }
   if constexpr (KS == 1) {
-    // x3 k1 GEMMs with M a multiple of 192 on 192 x 64 single-buffered tiles (154 VGPRs, three
-    // workgroups per CU; each x column block read 2x / 4x instead of 3x / 6x): 384 x 384 at
-    // T = 5568 602 -> 541 us, 768 x 768 at T = 696 253 -> 249 (profiles/r04x_k1_192_ab.txt).
-    // Tuning override VRVQ_CONV_K1X3_192=0 (128-row tiles) | 1 (default)
-    if (conv_k1x3_192() && a.w3 != nullptr && a.M % 192 == 0)
-      return launch_cfg<192, 64, 2, 4, KS>(a, batch, st);
-    // k = 1 GEMMs with M a multiple of 192 (the 384 / 768-channel ResidualUnit k1 + skip):
-    // 192-row tiles read each x column block 2x / 4x instead of 3x / 6x (tuning knob)
-    if (conv_k1_192() && a.w3 == nullptr && a.M % 192 == 0 && a.M % 128 == 0) {
-      if (bn == 64) return launch_cfg<192, 64, 2, 4, KS>(a, batch, st);
-      return launch_cfg<192, 128, 2, 4, KS>(a, batch, st);
-    }
+    // k = 1 GEMMs with M a multiple of 192 (the 384 / 768-channel ResidualUnit k1 + skip): 192-row
+    // tiles read each x column block 2x / 4x instead of 3x / 6x. x3: 192 x 64 single-buffered
+    // tiles (154 VGPRs, three workgroups per CU), 384 x 384 at T = 5568 602 -> 541 us, 768 x 768
+    // at T = 696 253 -> 249 (profiles/r04x_k1_192_ab.txt). fp32-input loop (M also a multiple of
+    // 128): 768 x 768 k1 + skip at T = 696 485 -> 386 us, 384: 930 -> 922; 256-row tiles for
+    // 512 / 768 were slower, 248 / 473 us (profiles/r01j_conv_k1_ab.txt).
+    if (x3 && a.M % 192 == 0) return launch_cfg<192, 64, 2, 4, KS>(a, batch, st, plan);
+    if (!x3 && a.M % 192 == 0 && a.M % 128 == 0) return launch_bn<192, 2, KS>(bn, a, batch, st, plan);
   }
-  if (bn == 64) return launch_cfg<128, 64, 2, 4, KS>(a, batch, st);
-  return launch_cfg<128, 128, 2, 4, KS>(a, batch, st);
+  return launch_bn<128, 2, KS>(bn, a, batch, st, plan);
 }
 
-int dispatch_ks(int ks, const ConvArgs& a, int batch, hipStream_t st) {
+int dispatch_ks(int ks, const ConvArgs& a, int batch, hipStream_t st, ConvPlan* plan) {
   switch (ks) {
-    case 1: return dispatch_tiles<1>(a, batch, st);
-    case 2: return dispatch_tiles<2>(a, batch, st);
-    case 3: return dispatch_tiles<3>(a, batch, st);
-    case 4: return dispatch_tiles<4>(a, batch, st);
-    case 7: return dispatch_tiles<7>(a, batch, st);
-    case 8: return dispatch_tiles<8>(a, batch, st);
-    case 16: return dispatch_tiles<16>(a, batch, st);
+    case 1: return dispatch_tiles<1>(a, batch, st, plan);
+    case 2: return dispatch_tiles<2>(a, batch, st, plan);
+    case 3: return dispatch_tiles<3>(a, batch, st, plan);
+    case 4: return dispatch_tiles<4>(a, batch, st, plan);
+    case 7: return dispatch_tiles<7>(a, batch, st, plan);
+    case 8: return dispatch_tiles<8>(a, batch, st, plan);
+    case 16: return dispatch_tiles<16>(a, batch, st, plan);
     default: return VRVQ_ERR_UNSUPPORTED;
   }
 }
@@ -949,6 +859,76 @@ extern "C" int vrvq_conv_last_launch(int out[5]) {
   return 0;
 }
 
+namespace {
+
+// The three conv entry points below their pointer checks, shared with vrvq_conv_plan (which
+// passes plan and, for the buffers a decision asks about, any non-null address).
+
+bool conv1d_geometry_ok(int batch, int cin, int tin, int cout, int cout_pad, int k, int stride,
+                        int pad, int dil, int tout) {
+  return batch > 0 && cin > 0 && tin > 0 && cout > 0 && k > 0 && stride > 0 && dil > 0 &&
+         pad >= 0 && tout > 0 && cout_pad >= cout && cout_pad % 128 == 0 &&
+         tout == ((long long)tin + 2LL * pad - (long long)dil * (k - 1) - 1) / stride + 1;
+}
+
+// a: the pointers of the call (w3, pj_part set where given). proj: vrvq_conv1d_proj, the MFMA
+// tiles only (their epilogue owns the projection).
+int run_conv1d(ConvArgs a, int batch, int cin, int tin, int cout, int cout_pad, int k, int stride,
+               int pad, int dil, int tout, int epilogue, void* workspace, long long ws_bytes,
+               hipStream_t st, ConvPlan* plan) {
+  const bool proj = a.pj_part != nullptr;
+  a.cin = cin; a.tin = tin; a.M = cout; a.m_pad = cout_pad; a.cout = cout;
+  a.stride = stride; a.pad = pad; a.dil = dil; a.ng = tout; a.up = 0; a.up_pad = 0;
+  a.ssh = 0;
+  if (stride > 1 && (stride & (stride - 1)) == 0)
+    while ((1 << a.ssh) < stride) ++a.ssh;
+  a.ylen = tout; a.epi = epilogue;
+  if (workspace != nullptr) {
+    long long need = 0;
+    const int rc = vrvq_conv1d_workspace(batch, cin, tin, cout, k, stride, pad, dil,
+                                         a.w3 != nullptr, &need);
+    if (rc) return rc;
+    VRVQ_CHECK_ARG(ws_bytes >= need);
+    if (need > 0) a.ks_part = static_cast<float*>(workspace);
+  }
+  if (a.w3 != nullptr && stride > 1) {
+    // strided conv on the x3 loop: a stride-1 k = 2 conv over the phase-split view of x
+    // (conv_core.h ConvArgs::psh); w_x3 holds the planes of W'[co][c*s + r][j] = W[co][c][j*s + r]
+    if (k != 2 * stride || a.ssh == 0 || pad >= stride) return VRVQ_ERR_UNSUPPORTED;
+    a.psh = a.ssh; a.ppad = pad; a.pcin = cin; a.ptin = tin;
+    a.cin = cin * stride; a.tin = tout + 1;
+    a.stride = 1; a.pad = 0; a.dil = 1; a.ssh = 0;
+    return dispatch_ks(2, a, batch, st, plan);
+  }
+  if (!proj && cout <= SMALL_COUT && stride == 1 &&
+      cin * k * (cout == 1 ? 1 : SMALL_COUT) <= SMALL_WMAX)
+    return launch_small(a, batch, k, st, plan);
+  if (!proj && cin == 1 && k == 7 && stride == 1 && dil == 1 && !a.alpha && cout % CI1_CG == 0 &&
+      tout % 4 == 0) {
+    const long long nblk =
+        (long long)batch * ((tout + 256 * CI1_T - 1) / (256 * CI1_T)) * (cout / CI1_CG);
+    if (nblk <= 0 || nblk > 0x7fffffffLL) return VRVQ_ERR_ARG;
+    if (plan) *plan = ConvPlan{PATH_CIN1, 0, 0, 0, k, 0, 0};
+    return launch_kernel(conv_cin1_stream_kernel<7>, nblk, 256, 0, st, a, plan != nullptr);
+  }
+  return dispatch_ks(k, a, batch, st, plan);
+}
+
+int run_conv_transpose1d(ConvArgs a, int batch, int cin, int tin, int cout, int cout_pad,
+                         int stride, int pad, hipStream_t st, ConvPlan* plan) {
+  VRVQ_CHECK_ARG(batch > 0 && cin > 0 && tin > 0 && cout > 0 && stride > 0);
+  // pad 0 = the padding=False windows of the chunked codec (models/dac_base.py:72-82)
+  VRVQ_CHECK_ARG(pad >= 0 && pad < stride);
+  VRVQ_CHECK_ARG(cout_pad >= cout * stride && cout_pad % 64 == 0);
+  a.cin = cin; a.tin = tin; a.M = cout * stride; a.m_pad = cout_pad; a.cout = cout;
+  a.stride = 1; a.pad = 1; a.dil = 1; a.ng = tin + 1; a.up = stride; a.up_pad = pad;
+  a.ylen = (tin - 1) * stride - 2 * pad + 2 * stride;
+  a.epi = VRVQ_EPI_NONE;
+  return dispatch_ks(2, a, batch, st, plan);
+}
+
+}  // namespace
+
 extern "C" int vrvq_conv1d_ws(const float* x, int batch, int cin, int tin, const float* alpha,
                               const float* inv_alpha, const float* w_packed,
                               const uint16_t* w_x3, int cout, int cout_pad, int k, int stride,
@@ -958,53 +938,16 @@ extern "C" int vrvq_conv1d_ws(const float* x, int batch, int cin, int tin, const
                               long long ws_bytes, vrvq_stream_t stream) {
   VRVQ_CHECK_ARG(x && w_packed && (y || y_snake));
   VRVQ_CHECK_ARG(y_snake == nullptr || (alpha_out && inv_alpha_out));
-  VRVQ_CHECK_ARG(batch > 0 && cin > 0 && tin > 0 && cout > 0 && k > 0 && stride > 0 &&
-                 dil > 0 && pad >= 0 && tout > 0);
-  VRVQ_CHECK_ARG(cout_pad >= cout && cout_pad % 128 == 0);
+  VRVQ_CHECK_ARG(conv1d_geometry_ok(batch, cin, tin, cout, cout_pad, k, stride, pad, dil, tout));
   VRVQ_CHECK_ARG(alpha == nullptr || inv_alpha != nullptr);
   VRVQ_CHECK_ARG(epilogue >= 0 && epilogue <= 2);
-  const long long expect = ((long long)tin + 2LL * pad - (long long)dil * (k - 1) - 1) / stride + 1;
-  VRVQ_CHECK_ARG(expect == tout);
   ConvArgs a{};
   a.x = x; a.alpha = alpha; a.inv_alpha = inv_alpha; a.w = w_packed;
   a.bias = bias; a.res = residual; a.y = y;
   a.alpha_o = alpha_out; a.inv_alpha_o = inv_alpha_out; a.ys = y_snake;
-  a.cin = cin; a.tin = tin; a.M = cout; a.m_pad = cout_pad; a.cout = cout;
-  a.stride = stride; a.pad = pad; a.dil = dil; a.ng = tout; a.up = 0; a.up_pad = 0;
-  a.ssh = 0;
-  if (stride > 1 && (stride & (stride - 1)) == 0)
-    while ((1 << a.ssh) < stride) ++a.ssh;
-  a.ylen = tout; a.epi = epilogue;
   a.w3 = reinterpret_cast<const unsigned*>(w_x3);
-  if (workspace != nullptr) {
-    long long need = 0;
-    const int rc = vrvq_conv1d_workspace(batch, cin, tin, cout, k, stride, pad, dil,
-                                         w_x3 != nullptr, &need);
-    if (rc) return rc;
-    VRVQ_CHECK_ARG(ws_bytes >= need);
-    if (need > 0) a.ks_part = static_cast<float*>(workspace);
-  }
-  if (w_x3 != nullptr && stride > 1) {
-    // strided conv on the x3 loop: a stride-1 k = 2 conv over the phase-split view of x
-    // (conv_core.h ConvArgs::psh); w_x3 holds the planes of W'[co][c*s + r][j] = W[co][c][j*s + r]
-    if (k != 2 * stride || a.ssh == 0 || pad >= stride) return VRVQ_ERR_UNSUPPORTED;
-    a.psh = a.ssh; a.ppad = pad; a.pcin = cin; a.ptin = tin;
-    a.cin = cin * stride; a.tin = tout + 1;
-    a.stride = 1; a.pad = 0; a.dil = 1; a.ssh = 0;
-    return dispatch_ks(2, a, batch, as_stream(stream));
-  }
-  if (cout <= SMALL_COUT && stride == 1 && cin * k * (cout == 1 ? 1 : SMALL_COUT) <= SMALL_WMAX)
-    return launch_small(a, batch, k, as_stream(stream));
-  if (cin == 1 && k == 7 && stride == 1 && dil == 1 && !alpha && cout % CI1_CG == 0 &&
-      tout % 4 == 0 && cin1_stream()) {
-    const long long nblk =
-        (long long)batch * ((tout + 256 * CI1_T - 1) / (256 * CI1_T)) * (cout / CI1_CG);
-    if (nblk <= 0 || nblk > 0x7fffffffLL) return VRVQ_ERR_ARG;
-    hipLaunchKernelGGL(conv_cin1_stream_kernel<7>, dim3((unsigned)nblk), dim3(256), 0,
-                       as_stream(stream), a);
-    return vrvq_launch_status();
-  }
-  return dispatch_ks(k, a, batch, as_stream(stream));
+  return run_conv1d(a, batch, cin, tin, cout, cout_pad, k, stride, pad, dil, tout, epilogue,
+                    workspace, ws_bytes, as_stream(stream), nullptr);
 }
 
 extern "C" int vrvq_conv1d_proj(const float* x, int batch, int cin, int tin, const float* alpha,
@@ -1020,29 +963,18 @@ extern "C" int vrvq_conv1d_proj(const float* x, int batch, int cin, int tin, con
   VRVQ_CHECK_ARG(alpha == nullptr || inv_alpha != nullptr);
   VRVQ_CHECK_ARG(((uintptr_t)part & 15) == 0 && ((uintptr_t)w3in & 15) == 0);
   if (cout != 1024 || nq > 32) return VRVQ_ERR_UNSUPPORTED;  // the latent (RD) / CH_NQMAX
-  const long long expect = (long long)tin + 2LL * pad - (long long)dil * (k - 1);
-  VRVQ_CHECK_ARG(expect == tout);
+  VRVQ_CHECK_ARG(conv1d_geometry_ok(batch, cin, tin, cout, cout_pad, k, 1, pad, dil, tout));
   VRVQ_CHECK_ARG((long long)batch * tout * nq * 8 * 8 < 0x7fffffffLL);
   ConvArgs a{};
   a.x = x; a.alpha = alpha; a.inv_alpha = inv_alpha; a.w = w_packed; a.bias = bias; a.y = y;
-  a.cin = cin; a.tin = tin; a.M = cout; a.m_pad = cout_pad; a.cout = cout;
-  a.stride = 1; a.pad = pad; a.dil = dil; a.ng = tout; a.up = 0; a.up_pad = 0; a.ssh = 0;
-  a.ylen = tout; a.epi = VRVQ_EPI_NONE;
   a.w3 = reinterpret_cast<const unsigned*>(w_x3);
   a.pj_w3 = reinterpret_cast<const unsigned*>(w3in);
   a.pj_part = part;
   a.pj_nq = nq;
   a.pj_nf = batch * tout;
-  if (workspace != nullptr) {  // split-K as vrvq_conv1d_ws (same shape, same parts)
-    long long need = 0;
-    const int rc = vrvq_conv1d_workspace(batch, cin, tin, cout, k, 1, pad, dil, w_x3 != nullptr,
-                                         &need);
-    if (rc) return rc;
-    VRVQ_CHECK_ARG(ws_bytes >= need);
-    if (need > 0) a.ks_part = static_cast<float*>(workspace);
-  }
-  // the MFMA tiles only (their epilogue owns the projection); every 1024-row tile is 128 rows
-  return dispatch_ks(k, a, batch, as_stream(stream));
+  // split-K as vrvq_conv1d_ws (same shape, same parts)
+  return run_conv1d(a, batch, cin, tin, cout, cout_pad, k, 1, pad, dil, tout, VRVQ_EPI_NONE,
+                    workspace, ws_bytes, as_stream(stream), nullptr);
 }
 
 extern "C" int vrvq_conv_transpose1d(const float* x, int batch, int cin, int tin,
@@ -1066,22 +998,52 @@ extern "C" int vrvq_conv_transpose1d_pad(const float* x, int batch, int cin, int
                                          float* y_snake, vrvq_stream_t stream) {
   VRVQ_CHECK_ARG(x && w_packed && (y || y_snake));
   VRVQ_CHECK_ARG(y_snake == nullptr || (alpha_out && inv_alpha_out));
-  VRVQ_CHECK_ARG(batch > 0 && cin > 0 && tin > 0 && cout > 0 && stride > 0);
-  // pad 0 = the padding=False windows of the chunked codec (models/dac_base.py:72-82)
-  VRVQ_CHECK_ARG(pad >= 0 && pad < stride);
-  VRVQ_CHECK_ARG(cout_pad >= cout * stride && cout_pad % 64 == 0);
   VRVQ_CHECK_ARG(alpha == nullptr || inv_alpha != nullptr);
-  const int p = pad;
   ConvArgs a{};
   a.x = x; a.alpha = alpha; a.inv_alpha = inv_alpha; a.w = w_packed; a.bias = bias;
   a.res = nullptr; a.y = y;
   a.alpha_o = alpha_out; a.inv_alpha_o = inv_alpha_out; a.ys = y_snake;
-  a.cin = cin; a.tin = tin; a.M = cout * stride; a.m_pad = cout_pad; a.cout = cout;
-  a.stride = 1; a.pad = 1; a.dil = 1; a.ng = tin + 1; a.up = stride; a.up_pad = p;
-  a.ylen = (tin - 1) * stride - 2 * p + 2 * stride;
-  a.epi = VRVQ_EPI_NONE;
   a.w3 = reinterpret_cast<const unsigned*>(w_x3);
-  return dispatch_ks(2, a, batch, as_stream(stream));
+  return run_conv_transpose1d(a, batch, cin, tin, cout, cout_pad, stride, pad, as_stream(stream),
+                              nullptr);
+}
+
+extern "C" int vrvq_conv_plan(int kind, int batch, int cin, int tin, int cout, int k, int stride,
+                              int pad, int dil, int has_x3, int has_workspace, int out[7]) {
+  VRVQ_CHECK_ARG(out && kind >= VRVQ_PLAN_CONV && kind <= VRVQ_PLAN_CONV_TRANSPOSE);
+  static float present[4];  // stands for every buffer a decision asks about; never dereferenced
+  ConvArgs a{};
+  a.w3 = has_x3 ? reinterpret_cast<const unsigned*>(present) : nullptr;
+  void* ws = has_workspace ? present : nullptr;
+  ConvPlan p{};
+  int rc;
+  if (kind == VRVQ_PLAN_CONV_TRANSPOSE) {
+    VRVQ_CHECK_ARG(stride > 0 && k == 2 * stride && dil == 1);
+    // the packers' padding (vrvq_pack_convt1d_weight callers: whole 128- or 192-row tiles)
+    const long long rows = (long long)cout * stride, rt = 128 % stride == 0 ? 128 : 192;
+    VRVQ_CHECK_ARG(cout > 0 && rows < 0x7fffff00LL);
+    rc = run_conv_transpose1d(a, batch, cin, tin, cout, (int)((rows + rt - 1) / rt * rt), stride,
+                              pad, nullptr, &p);
+  } else {
+    VRVQ_CHECK_ARG(cout > 0 && cout < 0x7fffff00 && k > 0 && stride > 0 && dil > 0 && tin > 0 &&
+                   pad >= 0);
+    const long long tout = ((long long)tin + 2LL * pad - (long long)dil * (k - 1) - 1) / stride + 1;
+    const int cout_pad = (cout + 127) / 128 * 128;
+    VRVQ_CHECK_ARG(tout > 0 && tout <= 0x7fffffffLL);
+    VRVQ_CHECK_ARG(conv1d_geometry_ok(batch, cin, tin, cout, cout_pad, k, stride, pad, dil,
+                                      (int)tout));
+    if (kind == VRVQ_PLAN_PROJ) {
+      VRVQ_CHECK_ARG(stride == 1);
+      if (cout != 1024) return VRVQ_ERR_UNSUPPORTED;
+      a.pj_part = present;
+    }
+    rc = run_conv1d(a, batch, cin, tin, cout, cout_pad, k, stride, pad, dil, (int)tout,
+                    VRVQ_EPI_NONE, ws, 0x7fffffffffffffffLL, nullptr, &p);
+  }
+  if (rc) return rc;
+  const int v[7] = {p.BM, p.BN, p.KS, p.x3, p.S, p.path, p.WM};
+  for (int i = 0; i < 7; ++i) out[i] = v[i];
+  return 0;
 }
 
 extern "C" int vrvq_pack_conv1d_weight(const float* w, int cout, int cin, int k, int cout_pad,

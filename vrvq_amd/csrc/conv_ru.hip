@@ -17,7 +17,6 @@
 #include "common.h"
 #include "conv_core.h"
 #include "conv_x3.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -32,7 +31,6 @@ struct RuArgs {
   const float* w1;     // [C][1][m_pad]  packed k=1 weight
   const u32x4* w1x3;   // pre-split W1 (vrvq_pack_x3_weight, k = 1) or null
   int C;
-  int p2h;             // ru_p2x3h tiles: phase 2 on the split MFMA in two K-halves (else fp32)
 };
 
 // Phase 2 on the split bf16 MFMA when its three hs planes (6 B per element) fit in the LDS
@@ -180,7 +178,7 @@ void ru_fused_kernel(RuArgs ra) {
   }
 
   if constexpr (X3 && ru_p2x3h<BM, BN, WM>()) {
-    if (ra.w1x3 != nullptr && ra.p2h) {
+    if (ra.w1x3 != nullptr) {
       // ---- phase 2 on the split bf16 MFMA in two K-halves (C = 128 at BN = 128: the three
       // planes of all 128 channels would take 96 KB). The wm = 0 waves hold rows [0, 64): they
       // write them as half 0's planes [plane][8 octets][BN][8] (48 KB); the wm = 1 waves park
@@ -363,37 +361,12 @@ void ru_fused_kernel(RuArgs ra) {
 // x3 phase 1 for every C <= 192 (C = 256: its 256-row weight stage leaves room for one
 // workgroup per CU; it keeps the fp32 path). Measured at B = 32 with the single-stage x3
 // loop: RU 96 2.12 -> 1.77 ms, RU 192 4.00 -> 3.15 ms, RU 128 1.97 -> 1.35 ms per unit
-// (profiles/r02zg_layer_table.txt). VRVQ_RU_X3=0: never, 1: C = 64 / 128 only, 2: all.
-static bool ru_x3_ok(int C) {
-  static const int v = [] {
-    const char* e = getenv("VRVQ_RU_X3");
-    return e ? atoi(e) : 2;
-  }();
-  return v == 2 ? true : v == 1 ? (C == 64 || C == 128) : false;
-}
-
-// tuning override: VRVQ_RU_BN64=1 runs the C = 64 / 128 units on 64-wide time tiles (more
-// workgroups per CU; C = 128 then fits phase 2 on the x3 MFMA) | 0 (default: 128-wide)
-static bool ru_bn64() {
-  static const bool v = [] {
-    const char* e = getenv("VRVQ_RU_BN64");
-    return e && atoi(e) != 0;
-  }();
-  return v;
-}
-
-// tuning override: VRVQ_RU_P2H=0 keeps the C = 128 unit's phase 2 on the fp32 MFMA (A/B)
-static bool ru_p2_halves() {
-  static const bool v = [] {
-    const char* e = getenv("VRVQ_RU_P2H");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-
+// (profiles/r02zg_layer_table.txt). The C = 64 / 128 units run 128-wide time tiles (64-wide
+// ones, more workgroups per CU: 724 -> 714 audio-sec/s end to end, profiles/r04q_sb_ab.txt);
+// C = 128 runs phase 2 in two K-halves on the split MFMA (from the fp32 phase 2: 1.36-1.48 ->
+// 1.22-1.27 ms per unit, profiles/r05ze_ru128_p2h_ab.txt).
 template <int BM, int BN, int WM, int NW>
 int launch_ru(RuArgs ra, int batch, hipStream_t st) {
-  ra.p2h = ru_p2_halves() ? 1 : 0;
   constexpr int CK = ChunkCfg<7, BM, BN>::CK;
   ConvArgs& a = ra.p1;
   a.n_mt = 1;
@@ -415,11 +388,10 @@ int launch_ru(RuArgs ra, int batch, hipStream_t st) {
     size_t lx = x3_lds_bytes<7, BM, BN>(XW, a.cin);
     if (lx < hsz) lx = hsz;
     if (ru_p2x3<BM, BN>() && ra.w1x3 != nullptr && lx < (size_t)BM * BN * 6) lx = (size_t)BM * BN * 6;
-    if (ru_p2x3h<BM, BN, WM>() && ra.w1x3 != nullptr && ru_p2_halves() &&
-        lx < (size_t)BM * BN * 5)
+    if (ru_p2x3h<BM, BN, WM>() && ra.w1x3 != nullptr && lx < (size_t)BM * BN * 5)
       lx = (size_t)BM * BN * 5;
     if (lx < epi) lx = epi;
-    if (a.w3 != nullptr && XW <= (BN - 1) + 6 * 9 + 1 && lx <= 160 * 1024 && ru_x3_ok(BM)) {
+    if (a.w3 != nullptr && XW <= (BN - 1) + 6 * 9 + 1 && lx <= 160 * 1024) {
       if (lx > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)ru_fused_kernel<BM, BN, WM, NW, true>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lx);
@@ -473,13 +445,9 @@ extern "C" int vrvq_residual_unit(const float* x, const float* x_snk, int batch,
   ra.C = channels;
   hipStream_t st = as_stream(stream);
   switch (channels) {
-    case 64:
-      if (ru_bn64()) return launch_ru<64, 64, 2, 4>(ra, batch, st);
-      return launch_ru<64, 128, 2, 4>(ra, batch, st);
+    case 64: return launch_ru<64, 128, 2, 4>(ra, batch, st);
     case 96: return launch_ru<96, 128, 1, 4>(ra, batch, st);
-    case 128:
-      if (ru_bn64()) return launch_ru<128, 64, 2, 4>(ra, batch, st);
-      return launch_ru<128, 128, 2, 4>(ra, batch, st);
+    case 128: return launch_ru<128, 128, 2, 4>(ra, batch, st);
     case 192: return launch_ru<192, 64, 2, 4>(ra, batch, st);
     case 256: return launch_ru<256, 64, 2, 4>(ra, batch, st);
     default: return VRVQ_ERR_UNSUPPORTED;

@@ -172,10 +172,12 @@ def level_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_co
     Encodes once (level 1), then for each level: hard mask of imp_map * (level * Nq),
     masked sum of z_q_is, bpf and kbps. The levels' z_q are decoded as batches of up to
     `max_decode_clips` clips (default: all L*B at once, the fastest; the reference decodes level
-    by level, so a cap of B keeps its peak decoder memory). Clips are independent, but a conv's
-    tile choice can depend on the batch size, so the per-level recon agrees with a per-level
-    decode within fp32 rounding, not bit for bit (tests/test_gpu_parity.py checks the batched
-    recon against the reference's per-level fixtures). Returns a list of dicts."""
+    by level, so a cap of B keeps its peak decoder memory). Clips are independent and a clip's
+    sums do not depend on the batch it runs in (DESIGN.md "Batch invariance": where a conv's
+    tile width follows the batch, both widths add K in the same order;
+    tests/test_gpu_parity.py test_batch_invariance_*), so the batched recon is the per-level
+    decode's (tests/test_gpu_parity.py checks it against the reference's per-level fixtures).
+    Returns a list of dicts."""
     n_q = model.n_codebooks
     with torch.no_grad():
         x = model.preprocess(audio, model.sample_rate)
