@@ -273,13 +273,9 @@ int vrvq_rvq_cross_prep(const float* w_in_t, const float* w_out, const float* b_
 int vrvq_rvq_frag(const float* cbn, int nq, int ncode, int cdim, float* cbf,
                   vrvq_stream_t stream);
 
-/* Projection kernel used by vrvq_rvq_project / vrvq_rvq_encode (both launch structures,
- * process-wide): 3 = one workgroup per clip x channel split on the bf16 matrix cores with both
- * operands split exactly into three bf16 terms (six products, fp32 accuracy; default); 2 = the
- * same unit on the fp32-input MFMA (an exact fmaf chain per split: the exactness fallback; also
- * VRVQ_RVQ_PROJECT=2 in the environment). 3 agrees with 2 to fp32 rounding. variant 0 queries.
- * Returns the previous variant (2 or 3), or VRVQ_ERR_ARG. */
-int vrvq_rvq_project_variant(int variant);
+/* The library reads no environment variable. The projection of vrvq_rvq_project /
+ * vrvq_rvq_encode is one kernel: one workgroup per clip x channel split on the bf16 matrix cores
+ * with both operands split exactly into three bf16 terms (six products, fp32 accuracy). */
 
 /* Bytes of the workspace vrvq_rvq_encode needs (projection partials + straight-through rows /
  * the fused launch's stage hand-off rows, whichever is larger). */
@@ -289,9 +285,9 @@ int vrvq_rvq_workspace(int batch, int frames, int nq, long long* bytes);
  * fused launch where the shape allows it (frames <= 96; up to 32 clips per launch, more clips
  * run as consecutive launches), else its three launches; vrvq_rvq_encode_part runs rvq_pt_kernel
  * per group of resident clips. 1 = never fused: vrvq_rvq_encode's three launches,
- * vrvq_rvq_encode_part's two (chain, expansion); also VRVQ_RVQ_FUSED=0 in the environment.
- * Every structure gives the same outputs bit for bit. path 0 queries. Returns the previous path
- * (1 or 2), or VRVQ_ERR_ARG. */
+ * vrvq_rvq_encode_part's two (chain, expansion): the A/B and the tests' reference. Every
+ * structure gives the same outputs bit for bit. path 0 queries. Returns the previous path (1 or
+ * 2), or VRVQ_ERR_ARG. */
 int vrvq_rvq_path(int path);
 
 /* The fused launches' in-kernel waits are bounded. A wait that runs out (a hang averted: it
@@ -350,6 +346,18 @@ int vrvq_rvq_encode_part(const float* part, int batch, int dim, int frames, int 
  * negative value removes the cap); returns the previous cap. */
 int vrvq_rvq_fused_clips(int frames, int nq, int ncode, int* clips);
 int vrvq_rvq_debug_capacity(int clips);
+
+/* Debug query (library version 105): the launch plan of a vrvq_rvq_encode_part call of this
+ * shape, filled by the function its launcher, vrvq_rvq_workspace_part and vrvq_rvq_fused_clips
+ * use. resident = workgroups of rvq_pt_kernel the device holds at once; given (> 0), the query
+ * is host-only and touches no device; 0 asks the current device (its occupancy query).
+ * out = {kind, F (frames per chain part, <= 16), P (parts per clip), n_fb (96-frame expansion
+ * windows per clip), workgroups per clip (P + 8 n_fb), dynamic LDS bytes, resident, clips per
+ * launch (0: chain + expand), launches, workspace bytes (= vrvq_rvq_workspace_part)}. The two
+ * process-wide test hooks, vrvq_rvq_path(1) and vrvq_rvq_debug_capacity, show in kind, clips
+ * and launches. Status as vrvq_rvq_workspace_part. */
+enum vrvq_rvq_plan_kind_t { VRVQ_RVQ_PLAN_PT = 0, VRVQ_RVQ_PLAN_CHAIN_EXPAND = 1 };
+int vrvq_rvq_plan(int batch, int frames, int nq, int ncode, int resident, long long out[10]);
 
 /* The whole quantizer, the replacement of VBRResidualVectorQuantize.forward's quantizer loop,
  * importance mask and masked sum (models/quantize.py:353-365, 389-421) and of

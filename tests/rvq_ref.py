@@ -53,11 +53,14 @@ def diverse_z(B, T, gen, D=D_MODEL):
 
 
 # (nq, ncode, B, T, vbr) of test_rvq_diverse_vs_fp64: every codebook size (N / 256 = 1 .. 4), odd
-# nq, nq = 1 / 28 / 32, partial frame tiles, T > 96, VBR and CBR
+# nq, nq = 1 / 28 / 32, partial frame tiles, T > 96, VBR and CBR; the last four are the shapes
+# only the retired projection-variant test covered (T = 97: the fused entry takes three launches
+# and the expansion two windows; one frame; odd nq at T = 200 and 40)
 DIVERSE_SHAPES = [
     (8, 1024, 3, 87, True), (32, 1024, 2, 87, True), (4, 256, 3, 40, True), (4, 512, 2, 87, True),
     (4, 768, 2, 40, False), (9, 1024, 2, 87, True), (1, 1024, 4, 87, False),
-    (8, 1024, 5, 200, True), (28, 1024, 2, 70, True), (8, 1024, 2, 13, True)]
+    (8, 1024, 5, 200, True), (28, 1024, 2, 70, True), (8, 1024, 2, 13, True),
+    (12, 1024, 2, 97, True), (2, 1024, 1, 1, True), (9, 1024, 2, 200, True), (5, 1024, 3, 40, True)]
 
 
 def diverse_case(nq, ncode, B, T, vbr=True):

@@ -31,7 +31,6 @@ def main():
     ap.add_argument("--frames", type=int, default=87)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--no-zqis", action="store_true", help="want_z_q_is=False (z_q only)")
-    ap.add_argument("--variants", default="3,2", help="projection kernel variants to time (2,3)")
     ap.add_argument("--paths", default="pt,2,1",
                     help="RVQ launch structures to time (pt: the launch from the conv's projection "
                          "partials, the eval encode's; on channel-major z: 2 fused, 1 three "
@@ -57,20 +56,14 @@ def main():
     run_pt = lambda: ops.rvq_encode_part(part, args.frames, st.b_in, st.cb, st.cbf, st.c2,  # noqa: E731
                                          st.w_out, st.b_out, st.mcol, st.qb, imp=imp, level=1.0,
                                          want_z_q_is=not args.no_zqis)
-    runs = []
-    for p in args.paths.split(","):
-        if p == "pt":
-            runs.append((p, 0))
-        else:
-            runs += [(int(p), int(x)) for x in args.variants.split(",")]
-    for path, v in runs:
+    for path in args.paths.split(","):
         if path == "pt":
             run = run_pt
             _lib.rvq_path(2)  # (a numeric path left at 1 would select pt's two-launch form)
         else:
             run = lambda: ops.rvq_encode(z, *st.codes_args(), imp=imp, level=1.0,  # noqa: E731
                                          want_z_q_is=not args.no_zqis)
-            _lib.rvq_project_variant(v)
+            path = int(path)
             _lib.rvq_path(path)
         ts = []
         for it in range(args.iters):
@@ -99,7 +92,7 @@ def main():
         _lib.rvq_timing(False)
         byt = rvq_bytes(args.batch, args.frames, args.nq, from_partials=path == "pt")
         tag = "rvq_encode no z_q_is" if args.no_zqis else "rvq_encode"
-        print(f"path {path} projection v{v} B={args.batch} nq={args.nq} T={args.frames}: {tag} median "
+        print(f"path {path} B={args.batch} nq={args.nq} T={args.frames}: {tag} median "
               f"{med:.1f} us (min {min(ts):.1f}), {byt / med / 1e3:.0f} GB/s algorithmic "
               f"({byt / med / 1e3 / 8000:.3f} of 8 TB/s), {byt / 1e6:.1f} MB; back to back "
               f"{b2b:.1f} us/call ({byt / b2b / 1e3 / 8000:.3f})"

@@ -18,6 +18,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import vrvq_amd  # noqa: E402
+from vrvq_amd import _lib  # noqa: E402
 from vrvq_amd.recipe import load_recipe  # noqa: E402
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,11 +76,10 @@ def main():
         n2 = ctypes.c_longlong(0)
         assert lib.vrvq_rvq_workspace_part(B, T, nq, 1024, ctypes.byref(n2)) == 0
         wsp = torch.empty((n2.value + 3) // 4, device=dev)
-        F_env = int(os.environ.get("VRVQ_RVQ_PT_F", "0"))
-        F = min(F_env, T) if 1 <= F_env <= 16 else min(16, T)  # pt_frames_per_part
-        P_parts = (T + F - 1) // F
-        n_fb = (T + 95) // 96
-        grid = B * (P_parts + 8 * n_fb)
+        plan = _lib.rvq_plan(B, T, nq, 1024)  # the product library's plan: the same geometry
+        assert plan["kind"] == _lib.RVQ_PLAN_PT and plan["launches"] == 1, plan
+        P_parts = plan["P"]
+        grid = B * plan["wg_per_clip"]
         stamps = torch.zeros(grid * 64, dtype=torch.int64, device=dev)
 
     def run(with_stamps):

@@ -95,7 +95,7 @@ SIGNATURES = {
                           _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, _P],
 }
 EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I),
-         "vrvq_rvq_project_variant": ([_I], _I), "vrvq_rvq_path": ([_I], _I),
+         "vrvq_rvq_path": ([_I], _I), "vrvq_rvq_plan": ([_I] * 5 + [_P], _I),
          "vrvq_rvq_sync_error": ([_P, _P], _I), "vrvq_rvq_timing": ([_I], _I),
          "vrvq_rvq_timing_read": ([_P, _P], _I), "vrvq_rvq_pending_error": ([_P], _I),
          "vrvq_rvq_debug": ([ctypes.c_uint, ctypes.c_uint], _I),
@@ -230,11 +230,15 @@ def rvq_timing_read():
     return float(ms.value), int(n.value)
 
 
-def rvq_project_variant(variant: int = 0) -> int:
-    """Select the RVQ projection kernel (3: clip x split workgroups on the split-bf16 MFMA,
-    default; 2: the same on the fp32 MFMA; 1: 48-frame tiles; 0: query). Returns the previous
-    variant. 1 and 2 write the same bits (tests/test_gpu_parity.py)."""
-    prev = load().vrvq_rvq_project_variant(variant)
-    if prev not in (1, 2, 3):
-        raise RuntimeError(f"vrvq_rvq_project_variant({variant}) failed ({prev})")
-    return prev
+RVQ_PLAN_KEYS = ("kind", "F", "P", "n_fb", "wg_per_clip", "lds", "resident", "clips", "launches",
+                 "ws_bytes")
+RVQ_PLAN_PT, RVQ_PLAN_CHAIN_EXPAND = 0, 1  # vrvq_rvq_plan_kind_t
+
+
+def rvq_plan(batch: int, frames: int, nq: int, ncode: int = 1024, resident: int = 0) -> dict:
+    """The launch plan of an rvq_encode_part call of this shape (include/vrvq.h vrvq_rvq_plan),
+    from the function that launches it. resident: workgroups of rvq_pt_kernel the device holds
+    at once (given: no GPU needed; 0: ask the current device). Keys: RVQ_PLAN_KEYS."""
+    out = (ctypes.c_longlong * 10)()
+    call("vrvq_rvq_plan", batch, frames, nq, ncode, resident, out)
+    return dict(zip(RVQ_PLAN_KEYS, (int(v) for v in out)))

@@ -14,9 +14,8 @@
 // chain parts and expansion in one launch for T <= 96). Both are built from the bodies of the
 // three-launch form, which stays as the reference path:
 //
-//   rvq_project{3,2}_kernel  P partials over 8 channel splits (one workgroup per clip x 96-frame
-//                        tile x split, the z slab staged once in LDS; 3: split-bf16 MFMA, 2:
-//                        fp32-input v_mfma_f32_16x16x4_f32).
+//   rvq_project3_kernel  P partials over 8 channel splits (one workgroup per clip x 96-frame
+//                        tile x split, the z slab staged once in LDS; split-bf16 MFMA).
 //   rvq_chain_kernel     the chain: <= 16 frames per workgroup, 8 waves; wave w scans its
 //                        N/8 codes for all frames at once on the matrix cores (16-code x
 //                        16-frame MFMA tiles), then 8 (frame, k) lane groups finish the stage
@@ -29,10 +28,15 @@
 // The distance is the reference's fp32 expression (dot in k order, fma(d, -2, e2) + c2, lowest
 // index on ties); the projection on the split-bf16 matrix cores (x3) is fp32-accurate but not
 // the reference's summation order, so the codes match every golden fixture BY TEST (full
-// batches included), not by construction: a near-tie could differ. The fp32-input projection
-// (vrvq_rvq_project_variant 2, rvq_project2_kernel) stays available as the exactness fallback.
+// batches included), not by construction: a near-tie could differ.
+//
+// The host side reads no environment variable. vrvq_rvq_encode_part's launch geometry (frames per
+// chain part, parts, expansion windows, LDS, clips per launch, workspace) is one RvqPlan
+// (rvq_plan), shared by the launcher, vrvq_rvq_workspace_part, vrvq_rvq_fused_clips and the
+// host-only query vrvq_rvq_plan; the kernels of a codebook size come from one table (rvq_kernels).
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -66,8 +70,6 @@ constexpr int RD = 1024;        // latent channels
 constexpr int RCD = 8;          // codebook_dim
 constexpr int PJ_SPLIT = 8;     // channel splits of the projection GEMM
 constexpr int PJ_CPS = RD / PJ_SPLIT;
-constexpr int PJ_KC = 32;       // channels per projection K chunk
-constexpr int PJ_NC = PJ_CPS / PJ_KC;  // K chunks per split (4)
 constexpr int CH_NT = 512;      // chain threads (8 waves)
 constexpr int CH_NW = CH_NT / 64;
 constexpr int CH_FMAX = 16;     // frames per chain workgroup
@@ -156,18 +158,12 @@ __global__ void rvq_frag_kernel(const float* __restrict__ cbn, int nq, int N,
 
 // ------------------------------------------------------------------------------------------
 // Projection: part[s][n][r] = sum_{c in split s} W_in_t[r/8][c][r%8] z[b][c][t], n = b*T + t,
-// r < R = nq*8, fp32-input form (variant 2). One workgroup per (clip, frame tile of <= 96,
-// channel split); each wave runs the split's 128 channels in order, 4 per
-// v_mfma_f32_16x16x4_f32, from a zero accumulator (an exact fmaf-chain order); a workgroup reads its z slab [128 ch][<= 96 t] from HBM once (row segments, staged in
-// LDS in four 32-channel chunks, each consumed as soon as it has landed) and keeps it for every
-// 64-row block of stages; the w_in_t operands go straight to registers (32 per lane and block).
-// 8 waves: wave w = 16-row tile (w & 3) x three 16-frame column tiles (w >> 2). 256 workgroups
-// at configs[1] (32 clips x 8 splits): one per CU, no second round.
-constexpr int PJ2_NT = 512;
-constexpr int PJ2_TC = 96;                      // frames per tile (6 MFMA column tiles)
-constexpr int PJ2_LD = 112;                     // z_s row stride (112 = 48 mod 64: lk groups
-                                                // of the B reads land on disjoint bank ranges)
-constexpr int PJ2_ZQ = PJ_KC * PJ2_TC / PJ2_NT; // z loads per thread per K chunk (6)
+// r < R = nq*8. One workgroup of 8 waves per (clip, frame tile of <= 96, channel split): it reads
+// its z slab [128 ch][<= 96 t] from HBM once and keeps it in LDS for every 16-row tile of the
+// stage rows; the w_in_t operands go straight to registers. 256 workgroups at configs[1]
+// (32 clips x 8 splits): one per CU, no second round.
+constexpr int PJ_NT = 512;
+constexpr int PJ_TC = 96;                       // frames per tile (6 MFMA column tiles)
 
 // Where the partials go: plain stores (the three-launch path: the chain reads them after a
 // kernel boundary) or, in the fused launch, tagged 8-B granules {partial, tag} written
@@ -190,111 +186,14 @@ struct PartSink {
   }
 };
 
-// One (clip b, frame tile tc, channel split s) projection unit; z_s = PJ_CPS * PJ2_LD floats
-// of LDS.
-__device__ __forceinline__ void project2_body(const float* __restrict__ z, int T, int nq, int tc,
-                                              int b, int s, const float* __restrict__ w_in_t,
-                                              const PartSink& out, int NF, float* z_s) {
-  const int R = nq * RCD;
-  const int t0 = tc * PJ2_TC;
-  const int ntl = min(PJ2_TC, T - t0);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 15, lk = lane >> 4;
-  const int rt = wave & 3, ch = wave >> 2;  // row tile, column-tile half
-  // A operands of row block rb: row r = 64 rb + 16 rt + lr (stage r / 8, k = r % 8), channels
-  // 4 j + lk of the split; rows >= R zeroed (clamped address, mask)
-  auto load_w = [&](int rb, float (&av)[PJ_CPS / 4]) {
-    const int r = rb * 64 + rt * 16 + lr;
-    const unsigned m = 0u - (unsigned)(r < R);
-    const float* wp = w_in_t + ((size_t)min(r >> 3, nq - 1) * RD + s * PJ_CPS + lk) * RCD + (r & 7);
-#pragma unroll
-    for (int j = 0; j < PJ_CPS / 4; ++j)
-      av[j] = __uint_as_float(__float_as_uint(wp[(size_t)4 * j * RCD]) & m);
-  };
-  float av[PJ_CPS / 4];
-  load_w(0, av);  // L2-resident weights first, their latency under the z slab's
-  const float* zb = z + ((size_t)b * RD + s * PJ_CPS) * T + t0;
-  {  // the slab: every load in flight at once
-    float zv[PJ_NC][PJ2_ZQ];
-#pragma unroll
-    for (int kc = 0; kc < PJ_NC; ++kc)
-#pragma unroll
-      for (int q = 0; q < PJ2_ZQ; ++q) {
-        const int e = tid + PJ2_NT * q;
-        const int c = e / PJ2_TC, t = e - c * PJ2_TC;
-        zv[kc][q] = zb[(size_t)(kc * PJ_KC + c) * T + min(t, ntl - 1)];  // clamped, zeroed below
-      }
-    __builtin_amdgcn_sched_barrier(0);  // every load issued before the first wait
-#pragma unroll
-    for (int kc = 0; kc < PJ_NC; ++kc)
-#pragma unroll
-      for (int q = 0; q < PJ2_ZQ; ++q) {
-        const int e = tid + PJ2_NT * q;
-        const int c = e / PJ2_TC, t = e - c * PJ2_TC;
-        z_s[(kc * PJ_KC + c) * PJ2_LD + t] =
-            __uint_as_float(__float_as_uint(zv[kc][q]) & (0u - (unsigned)(t < ntl)));
-      }
-  }
-  // a use of the weights here keeps their loads ahead of the slab's (issued first, they have
-  // landed by now); without it they are sunk below the barrier and waited for one by one
-#pragma unroll
-  for (int j = 0; j < PJ_CPS / 4; ++j) asm volatile("" ::"v"(av[j]));
-  __syncthreads();
-  for (int rb = 0; rb * 64 < R; ++rb) {
-    float an[PJ_CPS / 4];
-    const bool more = (rb + 1) * 64 < R;
-    if (more) load_w(rb + 1, an);  // next block's weights under this block's MFMAs
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < PJ_CPS / 4; ++j) {
-      const float* zr = z_s + (4 * j + lk) * PJ2_LD + ch * 48 + lr;
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], zr[q * 16], acc[q], 0, 0, 0);
-    }
-    // D layout: lane l, reg q -> row 4 (l >> 4) + q of the tile, frame l & 15
-    const int rr = rb * 64 + rt * 16 + 4 * lk;  // rows rr..rr+3 all valid iff rr < R
-    if (rr < R) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const int t = ch * 48 + q * 16 + lr;
-        if (t < ntl) {
-          const size_t n = (size_t)b * T + t0 + t;
-          out.put(((size_t)s * NF + n) * R + rr,
-                  make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]));
-        }
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int j = 0; j < PJ_CPS / 4; ++j) av[j] = an[j];
-    }
-  }
-}
-
-__global__ __launch_bounds__(PJ2_NT) void rvq_project2_kernel(const float* __restrict__ z, int T,
-                                                              int nq, int n_tc,
-                                                              const float* __restrict__ w_in_t,
-                                                              float* __restrict__ part, int NF) {
-  __shared__ __attribute__((aligned(16))) float z_s[PJ_CPS * PJ2_LD];
-  PartSink out{part, __builtin_amdgcn_make_buffer_rsrc(part, (short)0, 0, RSRC_FLAGS), 0u};
-  project2_body(z, T, nq, blockIdx.x % n_tc, blockIdx.x / n_tc, blockIdx.y, w_in_t, out, NF, z_s);
-}
-
-// ------------------------------------------------------------------------------------------
-// Projection on the bf16 matrix cores (variant 3): the same unit as rvq_project2_kernel (clip,
-// <= 96-frame tile, 128-channel split), with both operands split exactly into three bf16 terms
-// and the six products of conv_x3.h (dropped terms <= 2^-23 |ab|: fp32 accuracy) on
-// v_mfma_f32_16x16x32_bf16 -- 2.7x the fp32 MFMA rate for the GEMM that bounds the projection
-// (64 rows x 128 channels x 96 frames per unit). The z slab goes to LDS transposed, as three
+// One (clip b, frame tile tc, channel split s) projection unit on the bf16 matrix cores: both
+// operands split exactly into three bf16 terms and the six products of conv_x3.h (dropped terms
+// <= 2^-23 |ab|: fp32 accuracy) on v_mfma_f32_16x16x32_bf16 -- 2.7x the fp32 MFMA rate for the
+// GEMM that bounds the projection (64 rows x 128 channels x 96 frames per unit). The z slab goes to LDS transposed, as three
 // bf16 planes [plane][frame][channel] (rows of 128 channels + 8 pad: conflict-free 16-B B
 // reads); the W_in rows (8 channels per lane, L2) are split in registers.
 constexpr int PJ3_LDB = 136;                     // bf16 per frame row (272 B)
-constexpr int PJ3_PLANE = PJ2_TC * PJ3_LDB * 2;  // bytes per plane
+constexpr int PJ3_PLANE = PJ_TC * PJ3_LDB * 2;  // bytes per plane
 constexpr int PJ3_LDS = 3 * PJ3_PLANE;           // 78,336 B
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -324,11 +223,11 @@ __device__ __forceinline__ void project3_body(const float* __restrict__ z, int T
                                               int b, int s, const float* __restrict__ w_in_t,
                                               const PartSink& out, int NF, char* lds,
                                               unsigned long long* stamps = nullptr) {
-  constexpr int NIT = (PJ_CPS / 8) * PJ2_TC / PJ2_NT;  // (octet, frame) items per thread: 3
+  constexpr int NIT = (PJ_CPS / 8) * PJ_TC / PJ_NT;  // (octet, frame) items per thread: 3
   constexpr int NKS = PJ_CPS / 32;                      // K steps of 32 channels
   const int R = nq * RCD;
-  const int t0 = tc * PJ2_TC;
-  const int ntl = min(PJ2_TC, T - t0);
+  const int t0 = tc * PJ_TC;
+  const int ntl = min(PJ_TC, T - t0);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_rt = (R + 15) / 16;
@@ -353,16 +252,16 @@ __device__ __forceinline__ void project3_body(const float* __restrict__ z, int T
     float zv[NIT][8];
 #pragma unroll
     for (int q = 0; q < NIT; ++q) {
-      const int e = tid + PJ2_NT * q;
-      const int o = e / PJ2_TC, t = e - o * PJ2_TC;
+      const int e = tid + PJ_NT * q;
+      const int o = e / PJ_TC, t = e - o * PJ_TC;
 #pragma unroll
       for (int u = 0; u < 8; ++u) zv[q][u] = zb[(size_t)(8 * o + u) * T + min(t, ntl - 1)];
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < NIT; ++q) {
-      const int e = tid + PJ2_NT * q;
-      const int o = e / PJ2_TC, t = e - o * PJ2_TC;
+      const int e = tid + PJ_NT * q;
+      const int o = e / PJ_TC, t = e - o * PJ_TC;
       const unsigned m = 0u - (unsigned)(t < ntl);
       unsigned h[4], mm[4], l[4];
 #pragma unroll
@@ -384,7 +283,7 @@ __device__ __forceinline__ void project3_body(const float* __restrict__ z, int T
   __syncthreads();
   FSTAMP(stamps, 44);
   // work items (16-row tile rt, half hf = frame tiles 3 hf .. 3 hf + 2) over the 8 waves
-  for (int item = wave; item < 2 * n_rt; item += PJ2_NT / 64) {
+  for (int item = wave; item < 2 * n_rt; item += PJ_NT / 64) {
     const int rt = item >> 1, hf = item & 1;
     if (item != wave) load_w(rt, w);
     f32x4 acc[3];
@@ -437,7 +336,7 @@ __device__ __forceinline__ void project3_body(const float* __restrict__ z, int T
   }
 }
 
-__global__ __launch_bounds__(PJ2_NT) void rvq_project3_kernel(const float* __restrict__ z, int T,
+__global__ __launch_bounds__(PJ_NT) void rvq_project3_kernel(const float* __restrict__ z, int T,
                                                               int nq, int n_tc,
                                                               const float* __restrict__ w_in_t,
                                                               float* __restrict__ part, int NF) {
@@ -1088,36 +987,7 @@ struct FusedArgs {
   int dbg;                          // diagnostic build only: bit 0 = expansion skips its MFMAs,
                                     // bit 1 = chain parts skip the next stage's codebook
                                     // fragment loads (outputs wrong; timing only)
-  int warm;                         // expansion workgroups pull the stage tables into L2 first
-  int poll2;                        // rvq_pt_kernel's loader keeps two looks in flight
 };
-
-// The stage tables the chain and the expansion read after stage 0 (normalised / raw codebooks,
-// c2, M, W_out, b_out): inside the bench step the encoder's convs have evicted them from L2, and
-// the expansion workgroups idle until the chain's first stage anyway. Expansion workgroup e of
-// the launch touches slice (e / 8) of every table (workgroups are dealt to the 8 XCDs in turn,
-// so each XCD's L2 gets a whole copy); the loaded values feed a sum nothing uses.
-__device__ __forceinline__ void warm_tables(const FusedArgs& f, int e, int n_exp, int N,
-                                            float* sm) {
-  const int slices = max(1, n_exp / 8), k = (e / 8) % slices;
-  const size_t nq = (size_t)f.c.nq;
-  unsigned acc = 0;
-  auto touch = [&](const float* p, size_t n) {  // n floats, a multiple of 4
-    const size_t per = ((n / 4 + slices - 1) / slices) * 4;
-    const size_t lo = (size_t)k * per, hi = min(n, lo + per);
-    for (size_t i = lo + 4 * threadIdx.x; i < hi; i += 4 * blockDim.x) {
-      const float4 v = ld4(p + i);
-      acc ^= __float_as_uint(v.x) ^ __float_as_uint(v.w);
-    }
-  };
-  touch(f.c.cbf, nq * N * RCD);
-  touch(f.c.cb, nq * N * RCD);
-  touch(f.c.c2, nq * N);
-  touch(f.c.mcol, nq * nq * RCD * RCD);
-  touch(f.w_out, nq * RD * RCD);
-  touch(f.b_out, nq * RD);
-  if (acc == f.spin_max + 0x5a5a5a5au) sm[threadIdx.x] = __uint_as_float(acc);  // never in practice
-}
 
 // Expansion workgroup (clip b, frames [128 fb, +128), channels [128 cb, +128)): wave w =
 // 32-channel tile (w & 3) x 32-frame tiles {w >> 2, (w >> 2) + 2} of the block; per stage four
@@ -1170,6 +1040,49 @@ __device__ __forceinline__ void quad_transpose(f32x16& q, int lane) {
   }
 }
 
+// First frame of the 32-frame tile that nominally starts at tb: a clip's last, partial tile is
+// moved back to end at the clip's last frame (it overlaps the tile before it: those frames are
+// computed and written twice, with identical values), so every quad of four frames is whole from
+// T = 32 on.
+__device__ __forceinline__ int tile_first_frame(int tb, int T) {
+  return (tb + 32 > T && T >= 32) ? T - 32 : tb;
+}
+
+// The number of active stages (mask = i < n) of the output frames t0 .. t0 + 3 of clip b, one
+// per byte (frames past the clip re-read its last one: loaded, never stored).
+__device__ __forceinline__ unsigned active_stages4(const ChainArgs& c, int b, int t0) {
+  float sv[4];  // the loads first: one memory latency
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int t = min(max(t0 + u, 0), c.T - 1);
+    sv[u] = c.imp ? (c.imp[(size_t)b * c.T + t] * c.level) * (float)c.nq : INFINITY;
+  }
+  unsigned w = 0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    // mask[b,i,t] = (s - i >= 0) with s = (imp * level) * nq (models/utils.py:45-61). The
+    // fp32 difference rounds monotonically and 0 is exact, so that is s >= i: the first
+    // floor(s) + 1 stages (none for NaN or s < 0, all nq for s >= nq - 1 or CBR's inf)
+    const int n = sv[u] >= 0.0f ? (int)floorf(fminf(sv[u], (float)(c.nq - 1))) + 1 : 0;
+    w |= (unsigned)n << (8 * u);
+  }
+  return w;
+}
+
+// Four consecutive frames t .. t + 3 of one channel row: one 16-B store (rows of T floats are
+// dword-aligned); elementwise only where a clip is shorter than a frame tile (T < 32)
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void store_quad(float* row, int t, int T, float v0, float v1, float v2,
+                                           float v3) {
+  if (t + 4 <= T) {
+    *reinterpret_cast<f4u*>(row + t) = f4u{v0, v1, v2, v3};
+  } else if (t < T) {
+    row[t] = v0;
+    if (t + 1 < T) row[t + 1] = v1;
+    if (t + 2 < T) row[t + 2] = v2;
+  }
+}
+
 __device__ __forceinline__ void fused_expand_body(const FusedArgs& f, int e, float* sm) {
   const int nq = f.c.nq, T = f.c.T, F = f.c.F;
   constexpr int NCB = RD / FU_CB;
@@ -1206,29 +1119,10 @@ __device__ __forceinline__ void fused_expand_body(const FusedArgs& f, int e, flo
   unsigned nact[2];  // per output frame u: the number of active stages (mask = i < n), bytes
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    // the tile's first frame; a clip's last, partial tile is moved back to end at the clip's
-    // last frame (it overlaps the tile before it: those frames are computed and written twice,
-    // with identical values), so every quad of four frames is whole from T = 32 on
-    int tb = fb * FU_FB + (ft0 + 2 * j) * 32;
-    if (tb + 32 > T && T >= 32) tb = T - 32;
+    const int tb = tile_first_frame(fb * FU_FB + (ft0 + 2 * j) * 32, T);
     trow[j] = min(tb - wlo + col, FU_FB - 1);
     tq[j] = tb + 4 * (col >> 2);
-    float sv[4];  // the loads first: one memory latency
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int t = min(tq[j] + u, T - 1);
-      sv[u] = f.c.imp ? (f.c.imp[(size_t)b * T + t] * f.c.level) * (float)nq : INFINITY;
-    }
-    unsigned w = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      // mask[b,i,t] = (s - i >= 0) with s = (imp * level) * nq (models/utils.py:45-61). The
-      // fp32 difference rounds monotonically and 0 is exact, so that is s >= i: the first
-      // floor(s) + 1 stages (none for NaN or s < 0, all nq for s >= nq - 1 or CBR's inf)
-      const int n = sv[u] >= 0.0f ? (int)floorf(fminf(sv[u], (float)(nq - 1))) + 1 : 0;
-      w |= (unsigned)n << (8 * u);
-    }
-    nact[j] = w;
+    nact[j] = active_stages4(f.c, b, tq[j]);
   }
   const int zstage = f.P * FU_ROWS * RCD * 8;  // bytes per stage
   const float* wp = f.w_out + (size_t)(c0 + col) * RCD;  // A operand: channel row c0 + col
@@ -1246,18 +1140,6 @@ __device__ __forceinline__ void fused_expand_body(const FusedArgs& f, int e, flo
   auto late = [&](const u32x4& g, int i) -> bool {  // wave-uniform: a slice is not stage i's
     const unsigned tag = base + (unsigned)i + 1u;
     return __builtin_amdgcn_ballot_w64(!(g[1] == tag && g[3] == tag)) != 0;
-  };
-  // four consecutive frames of one channel: one 16-B store (rows of T floats are dword-
-  // aligned); elementwise only where a clip is shorter than a frame tile (T < 32)
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-  auto store_quad = [&](float* row, int t, float v0, float v1, float v2, float v3) {
-    if (t + 4 <= T) {
-      *reinterpret_cast<f4u*>(row + t) = f4u{v0, v1, v2, v3};
-    } else {
-      if (t < T) row[t] = v0;
-      if (t + 1 < T) row[t + 1] = v1;
-      if (t + 2 < T) row[t + 2] = v2;
-    }
   };
   f32x16 zq[2];
 #pragma unroll
@@ -1324,7 +1206,7 @@ __device__ __forceinline__ void fused_expand_body(const FusedArgs& f, int e, flo
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
           float* row = f.z_q_is + (((size_t)b * nq + i) * RD + chk + 8 * qd) * T;
-          store_quad(row, tq[j], q[4 * qd], q[4 * qd + 1], q[4 * qd + 2], q[4 * qd + 3]);
+          store_quad(row, tq[j], T, q[4 * qd], q[4 * qd + 1], q[4 * qd + 2], q[4 * qd + 3]);
         }
       }
 #pragma unroll
@@ -1345,7 +1227,7 @@ __device__ __forceinline__ void fused_expand_body(const FusedArgs& f, int e, flo
     for (int qd = 0; qd < 4; ++qd) {
       float* row = f.z_q + ((size_t)b * RD + chk + 8 * qd) * T;
       const float d = dead ? __builtin_nanf("") : 0.0f;
-      store_quad(row, tq[j], zq[j][4 * qd] + d, zq[j][4 * qd + 1] + d, zq[j][4 * qd + 2] + d,
+      store_quad(row, tq[j], T, zq[j][4 * qd] + d, zq[j][4 * qd + 1] + d, zq[j][4 * qd + 2] + d,
                  zq[j][4 * qd + 3] + d);
     }
   }
@@ -1364,7 +1246,7 @@ __device__ __forceinline__ ChainHandoff fused_handoff(const FusedArgs& f, int b,
   return hx;
 }
 
-template <int NM, bool PJ3>
+template <int NM>
 __global__ __launch_bounds__(CH_NT, 4) void rvq_fused_kernel(FusedArgs f) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int B = f.c.B, T = f.c.T, nq = f.c.nq, F = f.c.F;
@@ -1384,10 +1266,8 @@ __global__ __launch_bounds__(CH_NT, 4) void rvq_fused_kernel(FusedArgs f) {
   PartSink out{part, pr, f.epoch * 64u};
   if (f.stall && blk == 0)  // test knob (vrvq_rvq_debug_stall): a late producer
     for (unsigned k = 0; k < f.stall; ++k) __builtin_amdgcn_s_sleep(127);
-  if constexpr (PJ3)
-    project3_body(f.z, T, nq, 0, b, s, f.w_in_t, out, f.c.NF, reinterpret_cast<char*>(sm),
-                  f.stamps);
-  else project2_body(f.z, T, nq, 0, b, s, f.w_in_t, out, f.c.NF, sm);
+  project3_body(f.z, T, nq, 0, b, s, f.w_in_t, out, f.c.NF, reinterpret_cast<char*>(sm),
+                f.stamps);
   FSTAMP(f.stamps, 45);
   __syncthreads();  // the slab's LDS is the chain's from here
   // chain part s of clip b
@@ -1421,16 +1301,17 @@ __host__ __device__ inline int pj_nrt(int nq) { return (nq * RCD + 15) / 16; }
 // BEFORE its own tile's stores and checks the tags after them: vmcnt retires in order, so the
 // check waits for the poll only, not for the stores. r05's expansion polled from every wave,
 // and where a look came too early its second look waited behind the wave's whole stage of stores
-// (a ~1 us bubble per stage while the chain was ahead). The loader also pulls the stage tables
-// into its XCD's L2 while it waits for stage 0 (off by default: VRVQ_RVQ_WARM=1).
-constexpr int PT_FB = 96;                          // frames per expansion window (3 tiles)
+// (a ~1 us bubble per stage while the chain was ahead).
+constexpr int PT_FB = 96;                         // frames per expansion window (3 tiles)
 constexpr int PT_LOADER = 7;                       // the loader wave
 constexpr int PT_SLAB = PT_FB * RCD;               // floats per slab half
 constexpr int PT_SL = PT_FB * 4 / 64;              // 16-B granule pairs per loader lane (6)
 constexpr int PT_NI = 2;                           // tiles per wave, at most
-constexpr int PT_ZQ = 2 * PT_SLAB + CH_NT;         // floats: the z_q accumulators
+// floats: the z_q accumulators, CH_NT unused floats after the slab halves (nothing reads them;
+// they stay because the LDS bytes decide how many clips are resident)
+constexpr int PT_ZQ = 2 * PT_SLAB + CH_NT;
 constexpr int PT_NTILE = 12;                       // tiles of a window (4 x 3)
-constexpr int PT_EX_FLOATS = PT_ZQ + PT_NTILE * 16 * 64;  // slab, warm-up sink, accumulators
+constexpr int PT_EX_FLOATS = PT_ZQ + PT_NTILE * 16 * 64;  // slab halves, gap, accumulators
 
 struct PtOps {
   float wa[4];    // W_out[c0 + col][k], k = h, 2 + h, 4 + h, 6 + h (the MFMA steps' A values)
@@ -1447,7 +1328,7 @@ __device__ __forceinline__ int pt_tile(int w, int j) {
   return j == 0 ? 2 : -1;
 }
 
-__device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N, float* sm) {
+__device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, float* sm) {
   const int nq = f.c.nq, T = f.c.T, F = f.c.F;
   constexpr int NCB = RD / FU_CB;
   const int cb = e % NCB;
@@ -1491,26 +1372,9 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
   for (int j = 0; j < PT_NI; ++j) {
     const int ft = pt_tile(wave, j);
     act[j] = ft >= 0 && ft < n_ft;
-    // the tile's first frame; a clip's last, partial tile is moved back to end at the clip's last
-    // frame (it overlaps the tile before it: those frames are written twice, identical values)
-    int tb = fb * PT_FB + max(ft, 0) * 32;
-    if (tb + 32 > T && T >= 32) tb = T - 32;
+    const int tb = tile_first_frame(fb * PT_FB + max(ft, 0) * 32, T);
     tbs[j] = __builtin_amdgcn_readfirstlane(tb);
-    float sv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int t = min(max(tb + 4 * (col >> 2) + u, 0), T - 1);
-      sv[u] = f.c.imp ? (f.c.imp[(size_t)b * T + t] * f.c.level) * (float)nq : INFINITY;
-    }
-    unsigned w = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      // mask[b,i,t] = (s - i >= 0), s = (imp * level) * nq (models/utils.py:45-61): the first
-      // floor(s) + 1 stages (none for NaN or s < 0, all nq for s >= nq - 1 or CBR's inf)
-      const int n = sv[u] >= 0.0f ? (int)floorf(fminf(sv[u], (float)(nq - 1))) + 1 : 0;
-      w |= (unsigned)n << (8 * u);
-    }
-    nact[j] = w;
+    nact[j] = active_stages4(f.c, b, tb + 4 * (col >> 2));
   }
   // the lane's B-operand frame (col) as a slab row, and the first of its four output frames
   auto trow = [&](int j) { return min(max(tbs[j] - wlo + col, 0), PT_FB - 1); };
@@ -1521,16 +1385,6 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
     for (int s = 0; s < 4; ++s) o.wa[s] = wp[2 * s];
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) o.bb[qd] = f.b_out[(size_t)i * RD + chk + 8 * qd];
-  };
-  typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-  auto store_quad = [&](float* row, int t, float v0, float v1, float v2, float v3) {
-    if (t + 4 <= T) {
-      *reinterpret_cast<f4u*>(row + t) = f4u{v0, v1, v2, v3};
-    } else if (t < T) {  // a clip shorter than a frame tile
-      row[t] = v0;
-      if (t + 1 < T) row[t + 1] = v1;
-      if (t + 2 < T) row[t + 2] = v2;
-    }
   };
   // the masked z_q accumulators live in LDS ([slot][quad][lane] float4: conflict-free 16-B
   // accesses; in registers they spilled at the 128-VGPR budget with three tiles per wave, and a
@@ -1543,9 +1397,6 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
       for (int qd = 0; qd < 4; ++qd) zacc[(j * 4 + qd) * 64] = make_float4(0.f, 0.f, 0.f, 0.f);
   PtOps cur;
   load_ops(0, cur);
-  // idle until stage 0 lands (~6 us): the loader may pull the stage tables into this XCD's L2
-  // (fm kernel, r05) before its first poll
-  if (loader && f.warm) warm_tables(f, e, (int)gridDim.x - f.c.B * f.P, N, sm + 2 * PT_SLAB);
   __syncthreads();  // xdead_s initialised
   bool dead = false;
   u32x4 g[PT_SL];
@@ -1586,7 +1437,7 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
 #pragma unroll
           for (int qd = 0; qd < 4; ++qd) {
             float* row = f.z_q_is + (((size_t)b * nq + si) * RD + chk + 8 * qd) * T;
-            store_quad(row, tq(j), q[4 * qd], q[4 * qd + 1], q[4 * qd + 2], q[4 * qd + 3]);
+            store_quad(row, tq(j), T, q[4 * qd], q[4 * qd + 1], q[4 * qd + 2], q[4 * qd + 3]);
           }
         }
         float m[4];
@@ -1609,7 +1460,7 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
       if (si < 8) FSTAMP(f.stamps, 48 + si);  // the stage's stores issued (thread 0)
       cur = nxt;
     }
-    if (poll && f.poll2) {
+    if (poll) {
       // two looks in flight: while one look's loads are checked the next one is already on its
       // way, so a stage that lands just after a look is seen half a round trip later instead of
       // a whole one (each sc1 look crosses to the chain part's XCD: ~1-2 us)
@@ -1646,27 +1497,6 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
       if (in_h)
 #pragma unroll
         for (int u = 0; u < PT_SL; ++u) g[u] = h[u];
-    } else if (poll) {  // one look in flight (VRVQ_RVQ_POLL2=0, the A/B)
-      for (unsigned it = 0;; ++it) {
-        bool ok = true;
-#pragma unroll
-        for (int u = 0; u < PT_SL; ++u) ok = ok && g[u][1] == tag && g[u][3] == tag;
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-        if (it >= f.spin_max) {
-          if (lane == 0) {
-            report_timeout(f.sync + SYNC_ERR, f.err_host, 2u);
-            xdead_s = 1;
-          }
-          dead = true;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-#pragma unroll
-        for (int u = 0; u < PT_SL; ++u)
-          g[u] = __builtin_amdgcn_raw_buffer_load_b128(zr, soff(u) + i * zstage, 0, CPOL_SC1);
-      }
-    }
-    if (poll) {
       if (i < 8) FSTAMPT(f.stamps, 56 + i, 64 * PT_LOADER);  // the stage's rows seen
       float* slab = sm + (i & 1) * PT_SLAB;
 #pragma unroll
@@ -1688,7 +1518,7 @@ __device__ __forceinline__ void pt_expand_body(const FusedArgs& f, int e, int N,
       float* row = f.z_q + ((size_t)b * RD + chk + 8 * qd) * T;
       const float d = dead ? __builtin_nanf("") : 0.0f;
       const float4 a = zacc[(j * 4 + qd) * 64];
-      store_quad(row, tq(j), a.x + d, a.y + d, a.z + d, a.w + d);
+      store_quad(row, tq(j), T, a.x + d, a.y + d, a.z + d, a.w + d);
     }
   }
 }
@@ -1700,7 +1530,7 @@ __global__ __launch_bounds__(CH_NT, 4) void rvq_pt_kernel(FusedArgs f) {
   const int blk = blockIdx.x;
   FSTAMP(f.stamps, 0);
   if (blk >= B * f.P) {
-    pt_expand_body(f, blk - B * f.P, 256 * NM, sm);
+    pt_expand_body(f, blk - B * f.P, sm);
     FSTAMP(f.stamps, 41);
     return;
   }
@@ -1712,53 +1542,41 @@ __global__ __launch_bounds__(CH_NT, 4) void rvq_pt_kernel(FusedArgs f) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Projection kernel: 3 = rvq_project3_kernel (split-bf16 matrix cores, default), 2 =
-// rvq_project2_kernel (fp32-input MFMA: the exactness fallback, VRVQ_RVQ_PROJECT=2).
-int g_project_variant = 0;  // 0: not yet read from the environment
+// Host side. The codebook size (NM = ncode / 256) is a template parameter of the three kernels
+// that scan a codebook and of nothing on the host: one table, indexed by the size
+// (rvq_shape_ok: 256, 512, 768 or 1024 codes).
+struct RvqKernels {
+  void (*chain)(ChainArgs);
+  void (*fused)(FusedArgs);
+  void (*pt)(FusedArgs);
+};
 
-int project_variant() {
-  if (g_project_variant == 0) {
-    const char* e = getenv("VRVQ_RVQ_PROJECT");
-    g_project_variant = (e && e[0] == '2') ? 2 : 3;
-  }
-  return g_project_variant;
+const RvqKernels& rvq_kernels(int ncode) {
+  static const RvqKernels table[4] = {
+      {rvq_chain_kernel<1>, rvq_fused_kernel<1>, rvq_pt_kernel<1>},
+      {rvq_chain_kernel<2>, rvq_fused_kernel<2>, rvq_pt_kernel<2>},
+      {rvq_chain_kernel<3>, rvq_fused_kernel<3>, rvq_pt_kernel<3>},
+      {rvq_chain_kernel<4>, rvq_fused_kernel<4>, rvq_pt_kernel<4>}};
+  return table[ncode / 256 - 1];
 }
 
 int launch_project(const float* z, int batch, int frames, int nq, const float* w_in_t,
                    float* part, hipStream_t st) {
   const long long nf = (long long)batch * frames;
   VRVQ_CHECK_ARG(nf * nq * RCD * PJ_SPLIT < 0x7fffffffLL);
-  const int n_tc = (frames + PJ2_TC - 1) / PJ2_TC;
+  const int n_tc = (frames + PJ_TC - 1) / PJ_TC;
   VRVQ_CHECK_ARG((long long)batch * n_tc < 0x7fffffffLL);
-  if (project_variant() == 3) {
-    hipError_t e = hipFuncSetAttribute((const void*)rvq_project3_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PJ3_LDS);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(rvq_project3_kernel, dim3((unsigned)(batch * n_tc), PJ_SPLIT), dim3(PJ2_NT),
-                       PJ3_LDS, st, z, frames, nq, n_tc, w_in_t, part, (int)nf);
-  } else {
-    hipLaunchKernelGGL(rvq_project2_kernel, dim3((unsigned)(batch * n_tc), PJ_SPLIT), dim3(PJ2_NT),
-                       0, st, z, frames, nq, n_tc, w_in_t, part, (int)nf);
-  }
+  hipError_t e = hipFuncSetAttribute((const void*)rvq_project3_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, PJ3_LDS);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(rvq_project3_kernel, dim3((unsigned)(batch * n_tc), PJ_SPLIT), dim3(PJ_NT),
+                     PJ3_LDS, st, z, frames, nq, n_tc, w_in_t, part, (int)nf);
   return vrvq_launch_status();
 }
 
 unsigned long long* g_stamps = nullptr;   // diagnostic build: vrvq_debug_set_stamps
 unsigned long long* g_fstamps = nullptr;  // diagnostic build: vrvq_debug_set_fused_stamps
 int g_fdbg = 0;                           // diagnostic build: vrvq_debug_set_fused_flags
-
-template <int NM>
-int launch_chain_nm(const ChainArgs& a, hipStream_t st, long long nblk) {
-  const size_t lds = (size_t)ChainLds(a.nq, a.F, 256 * NM).total * sizeof(float);
-  if (lds > 160 * 1024) return VRVQ_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)rvq_chain_kernel<NM>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(rvq_chain_kernel<NM>, dim3((unsigned)nblk), dim3(CH_NT), lds, st, a);
-  return vrvq_launch_status();
-}
 
 int launch_chain(const ChainArgs& a0, int ncode, hipStream_t st) {
   ChainArgs a = a0;
@@ -1774,21 +1592,23 @@ int launch_chain(const ChainArgs& a0, int ncode, hipStream_t st) {
   a.NFS = a.NFS ? a.NFS : (int)nf;
   const long long nblk = (nf + F - 1) / F;
   VRVQ_CHECK_ARG(nblk < 0x7fffffffLL);
-  switch (ncode / 256) {
-    case 1: return launch_chain_nm<1>(a, st, nblk);
-    case 2: return launch_chain_nm<2>(a, st, nblk);
-    case 3: return launch_chain_nm<3>(a, st, nblk);
-    default: return launch_chain_nm<4>(a, st, nblk);
+  const size_t lds = (size_t)ChainLds(a.nq, a.F, ncode).total * sizeof(float);
+  if (lds > 160 * 1024) return VRVQ_ERR_UNSUPPORTED;
+  const auto kern = rvq_kernels(ncode).chain;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
   }
+  hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(CH_NT), lds, st, a);
+  return vrvq_launch_status();
 }
 
-int launch_expand(const float* zst, int batch, int dim, int frames, int nq, const float* w_out,
-                  const float* b_out, const float* imp, float level, float* z_q_is, float* z_q,
-                  float* mask, hipStream_t st, const float* mask_in = nullptr) {
-  ExpandArgs a{zst, batch, dim, frames, nq, w_out, b_out, imp, level, mask_in, z_q_is, z_q, mask};
-  a.n_ct = (dim + 31) / 32;
-  a.n_tt = (frames + 31) / 32;
-  const long long nblk = (long long)batch * a.n_tt * ((a.n_ct + 3) / 4);
+// a: every field but the tile counts
+int launch_expand(ExpandArgs a, hipStream_t st) {
+  a.n_ct = (a.D + 31) / 32;
+  a.n_tt = (a.T + 31) / 32;
+  const long long nblk = (long long)a.B * a.n_tt * ((a.n_ct + 3) / 4);
   VRVQ_CHECK_ARG(nblk < 0x7fffffffLL);
   hipLaunchKernelGGL(rvq_expand_kernel, dim3((unsigned)nblk), dim3(256), 0, st, a);
   return vrvq_launch_status();
@@ -1810,17 +1630,9 @@ size_t zst_floats(int batch, int frames, int nq) {
 }
 
 // ---- fused path, host side -----------------------------------------------------------------
-// 1: three launches everywhere; 2: the fused launch where the shape allows (default;
-// VRVQ_RVQ_FUSED=0 in the environment or vrvq_rvq_path(1) for the A/B).
-int g_rvq_path = 0;
-
-int rvq_path() {
-  if (g_rvq_path == 0) {
-    const char* e = getenv("VRVQ_RVQ_FUSED");
-    g_rvq_path = (e && e[0] == '0') ? 1 : 2;
-  }
-  return g_rvq_path;
-}
+// 1: three launches everywhere (vrvq_rvq_path(1), the A/B and the tests' reference); 2: the
+// fused launch where the shape allows (default).
+int g_rvq_path = 2;
 
 // Process-wide state of the fused launches' in-launch hand-offs:
 //  * epochs: ONE counter for every call of the process (every stream and device), so tags are
@@ -1927,10 +1739,11 @@ bool fused_prepare(hipStream_t st, size_t bytes, void* caller_ws, size_t caller_
   return true;
 }
 
-// Clips per fused launch: every workgroup resident at once, so that no waiting workgroup can
-// hold the slot of one it waits for (occupancy query with the launch's dynamic LDS, after the
-// attribute that allows it; cached per device, kernel and LDS size).
-int fused_clip_capacity(const void* kern, size_t lds, int wg_per_clip) {
+// Workgroups of `kern` the current device holds resident at once. A fused launch takes no more
+// clips than fit in them, so that no waiting workgroup can hold the slot of one it waits for
+// (occupancy query with the launch's dynamic LDS, after the attribute that allows it; cached per
+// device, kernel and LDS size). 0: the query failed.
+int resident_workgroups(const void* kern, size_t lds) {
   static std::mutex mu;
   static std::map<std::tuple<int, const void*, size_t>, int> cache;
   int device = 0;
@@ -1938,21 +1751,15 @@ int fused_clip_capacity(const void* kern, size_t lds, int wg_per_clip) {
   std::lock_guard<std::mutex> guard(mu);
   const auto key = std::make_tuple(device, kern, lds);
   auto it = cache.find(key);
-  int per_cu = 0;
-  if (it != cache.end()) {
-    per_cu = it->second;
-  } else {
-    int cus = 0, per = 0;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, CH_NT, lds) != hipSuccess)
-      cus = per = 0;
-    per_cu = cus * per;  // resident workgroups on the device
-    cache[key] = per_cu;
-  }
-  return per_cu / wg_per_clip;
+  if (it != cache.end()) return it->second;
+  int cus = 0, per = 0;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, CH_NT, lds) != hipSuccess)
+    cus = per = 0;
+  return cache[key] = cus * per;
 }
 
 constexpr int FUSED_NA = -1;  // the fused launch does not apply: take the three launches
@@ -1992,27 +1799,43 @@ int launch_timed(K kern, unsigned grid, size_t lds, hipStream_t st, const FusedA
   return vrvq_launch_status();
 }
 
+// The per-call arguments of vrvq_rvq_encode / vrvq_rvq_encode_part (whole batch); the weight
+// tables travel in a FusedArgs the entry point fills once.
+struct RvqCall {
+  int batch, frames, nq, ncode;
+  const float* z;     // [B][D][T] (vrvq_rvq_encode) or null
+  const float* part;  // [8][B T][nq 8] (vrvq_rvq_encode_part) or null
+  const float* imp;   // or null
+  int64_t* codes;
+  float* latents;
+  float* loss_pf;
+  float* z_q_is;      // or null
+  float* z_q;
+  float* mask;        // or null
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t st;
+};
+
 // Chunk of clips [b0, b0 + bc) of a fused launch: the outputs and inputs offset to it.
-void fused_chunk_args(FusedArgs& f, int b0, int bc, int frames, int nq, int F, const float* z,
-                      const float* imp, int64_t* codes, float* latents, float* loss_pf,
-                      float* z_q_is, float* z_q, float* mask) {
-  const size_t DT = (size_t)RD * frames;
+void fused_chunk_args(FusedArgs& f, const RvqCall& a, int b0, int bc, int F) {
+  const size_t T = (size_t)a.frames, DT = RD * T, nq = (size_t)a.nq;
   ChainArgs& c = f.c;
   c.B = bc;
-  c.T = frames;
-  c.nq = nq;
+  c.T = a.frames;
+  c.nq = a.nq;
   c.F = F;
-  c.NF = bc * frames;
-  c.imp = imp ? imp + (size_t)b0 * frames : nullptr;
-  c.codes = codes + (size_t)b0 * nq * frames;
-  c.latents = latents + (size_t)b0 * nq * RCD * frames;
-  c.loss_pf = loss_pf + (size_t)b0 * nq * frames;
+  c.NF = bc * a.frames;
+  c.imp = a.imp ? a.imp + b0 * T : nullptr;
+  c.codes = a.codes + b0 * nq * T;
+  c.latents = a.latents + b0 * nq * RCD * T;
+  c.loss_pf = a.loss_pf + b0 * nq * T;
   c.zst = nullptr;
-  c.mask = mask ? mask + (size_t)b0 * nq * frames : nullptr;
+  c.mask = a.mask ? a.mask + b0 * nq * T : nullptr;
   c.stamps = nullptr;
-  f.z = z + b0 * DT;
-  f.z_q_is = z_q_is ? z_q_is + (size_t)b0 * nq * DT : nullptr;
-  f.z_q = z_q + b0 * DT;
+  f.z = a.z ? a.z + b0 * DT : nullptr;
+  f.z_q_is = a.z_q_is ? a.z_q_is + b0 * nq * DT : nullptr;
+  f.z_q = a.z_q + b0 * DT;
   f.err_host = g_err_host_dev;
   f.spin_max = g_spin_max;
   f.stall = g_stall;
@@ -2021,131 +1844,132 @@ void fused_chunk_args(FusedArgs& f, int b0, int bc, int frames, int nq, int F, c
 }
 
 size_t zsh_bytes(int bc, int nq, int P) { return (size_t)bc * nq * P * FU_ROWS * RCD * 8; }
+size_t pt_zst_bytes(int batch, int frames, int nq) { return (size_t)batch * nq * frames * RCD * 4; }
 
-template <int NM, bool PJ3>
-int launch_fused_nm(const FusedArgs& f0, int batch, int frames, int nq, const float* z,
-                    const float* imp, int64_t* codes, float* latents, float* loss_pf,
-                    float* z_q_is, float* z_q, float* mask, float* ws, size_t ws_bytes,
-                    hipStream_t st) {
-  const int F = (frames + FU_NP - 1) / FU_NP;
-  size_t lds = (size_t)ChainLds(nq, F, 256 * NM).total * sizeof(float);
-  const size_t lds_pj = PJ3 ? (size_t)PJ3_LDS : (size_t)PJ_CPS * PJ2_LD * sizeof(float);
-  if (lds < lds_pj) lds = lds_pj;
+// vrvq_rvq_encode's fused launch (rvq_fused_kernel, frames <= 96), <= 32 resident clips per
+// launch; FUSED_NA where it does not apply.
+int launch_fused(const FusedArgs& f0, const RvqCall& a) {
+  const int F = (a.frames + FU_NP - 1) / FU_NP;
+  size_t lds = (size_t)ChainLds(a.nq, F, a.ncode).total * sizeof(float);
+  if (lds < (size_t)PJ3_LDS) lds = PJ3_LDS;
   if (lds < (size_t)FU_EX_LDS) lds = FU_EX_LDS;
   if (lds > 80 * 1024) return FUSED_NA;
-  const void* kern = (const void*)rvq_fused_kernel<NM, PJ3>;
-  const int cap = min(FU_CLIPS_MAX, fused_clip_capacity(kern, lds, 2 * FU_NP));
+  const auto kern = rvq_kernels(a.ncode).fused;
+  const int cap = min(FU_CLIPS_MAX, resident_workgroups((const void*)kern, lds) / (2 * FU_NP));
   if (cap < 1) return FUSED_NA;
-  const int bc_max = min(batch, cap);
-  const size_t part_b = 2 * part_floats((long long)bc_max * frames, nq) * sizeof(float);
-  const size_t need = part_b + zsh_bytes(bc_max, nq, FU_NP);
-  for (int b0 = 0; b0 < batch; b0 += bc_max) {
-    const int bc = min(bc_max, batch - b0);
+  const int bc_max = min(a.batch, cap);
+  const size_t part_b = 2 * part_floats((long long)bc_max * a.frames, a.nq) * sizeof(float);
+  const size_t need = part_b + zsh_bytes(bc_max, a.nq, FU_NP);
+  for (int b0 = 0; b0 < a.batch; b0 += bc_max) {
+    const int bc = min(bc_max, a.batch - b0);
     FusedArgs f = f0;
     FusedLaunch L;
-    if (!fused_prepare(st, need, ws, ws_bytes, &L)) {
+    if (!fused_prepare(a.st, need, a.ws, a.ws_bytes, &L)) {
       if (b0 == 0) return FUSED_NA;
       return VRVQ_ERR_UNSUPPORTED;  // cannot happen after a first successful chunk
     }
-    fused_chunk_args(f, b0, bc, frames, nq, F, z, imp, codes, latents, loss_pf, z_q_is, z_q, mask);
+    fused_chunk_args(f, a, b0, bc, F);
     f.sync = L.sync;
     f.epoch = L.epoch;
     f.c.part = reinterpret_cast<float*>(L.area);  // tagged granules: 2 floats per partial
     f.zsh = reinterpret_cast<unsigned long long*>(L.area + part_b);
-    f.zsh_bytes = (int)zsh_bytes(bc, nq, FU_NP);
+    f.zsh_bytes = (int)zsh_bytes(bc, a.nq, FU_NP);
     f.P = FU_NP;
     f.n_fb = 1;
-    const int rc = launch_timed(rvq_fused_kernel<NM, PJ3>, (unsigned)(2 * bc * FU_NP), lds, st, f);
+    const int rc = launch_timed(kern, (unsigned)(2 * bc * FU_NP), lds, a.st, f);
     if (rc) return rc;
   }
   return 0;
 }
 
-// Frames per chain part of rvq_pt_kernel: 16, fewer wherever the chain's LDS would not fit twice
-// per CU (beside an expansion workgroup).
-size_t pt_lds_bytes(int nq, int F, int N) {
-  size_t c = (size_t)ChainLds(nq, F, N).total * sizeof(float);
-  const size_t ex = (size_t)PT_EX_FLOATS * sizeof(float);  // slab, warm-up sink, one z_q tile
-  return c < ex ? ex : c;
-}
-int pt_frames_per_part(int frames, int nq, int N) {
-  static const int f_env = [] {  // VRVQ_RVQ_PT_F: frames per chain part (A/B; 1..16)
-    const char* e = getenv("VRVQ_RVQ_PT_F");
-    const int v = e ? atoi(e) : 0;
-    return v >= 1 && v <= FU_ROWS ? v : 0;
-  }();
-  // 16 frames per part: fewer, longer chain parts measured fastest at T = 87 (in-step 43.1-43.5
-  // us vs 44.2 at F = 11, 44.4-44.8 at 12; profiles/r06g_ab.txt)
-  const int F0 = f_env ? min(f_env, frames) : min(FU_ROWS, frames);
-  for (int F = F0; F >= 1; --F)
-    if (pt_lds_bytes(nq, F, N) <= 80 * 1024) return F;
-  return 0;
-}
-size_t pt_zst_bytes(int batch, int frames, int nq) { return (size_t)batch * nq * frames * RCD * 4; }
+// The launch plan of vrvq_rvq_encode_part: everything its launcher, its workspace size
+// (vrvq_rvq_workspace_part) and the queries (vrvq_rvq_fused_clips, vrvq_rvq_plan) need to agree
+// on, worked out here and nowhere else.
+enum { PLAN_PT = VRVQ_RVQ_PLAN_PT, PLAN_CHAIN_EXPAND = VRVQ_RVQ_PLAN_CHAIN_EXPAND };
+struct RvqPlan {
+  int kind = PLAN_CHAIN_EXPAND;  // rvq_pt_kernel per group of resident clips | chain, then expand
+  int F = 0, P = 0, n_fb = 0;    // frames per chain part; parts and 96-frame windows per clip
+  int wpc = 0;                   // workgroups per clip: P parts + 8 channel blocks x n_fb windows
+  int lds = 0;                   // dynamic LDS bytes of rvq_pt_kernel
+  int resident = 0;              // workgroups the device holds at once (0: not asked)
+  int clips = 0;                 // clips per launch (0: chain + expand)
+  int launches = 2;
+  long long ws_bytes = 0;        // the larger of the captured launch's granules + sync block and
+                                 // the two launches' zst rows
+};
 
-// Clips per rvq_pt_kernel launch (every workgroup resident), 0 when not even one clip fits or the
-// three launches are selected (vrvq_rvq_path(1)).
-template <int NM>
-int pt_capacity(int frames, int nq, int* F_out, int* P_out, int* n_fb_out, size_t* lds_out) {
-  const int F = pt_frames_per_part(frames, nq, 256 * NM);
-  if (F < 1 || rvq_path() == 1) return 0;
-  const int P = (frames + F - 1) / F;
-  const int n_fb = (frames + PT_FB - 1) / PT_FB;
-  const size_t lds = pt_lds_bytes(nq, F, 256 * NM);
-  const int wpc = P + (RD / FU_CB) * n_fb;
-  *F_out = F;
-  *P_out = P;
-  *n_fb_out = n_fb;
-  *lds_out = lds;
-  return min(fused_clip_capacity((const void*)rvq_pt_kernel<NM>, lds, wpc), g_pt_cap_limit);
+constexpr int RESIDENT_QUERY = 0;   // rvq_plan's `resident`: ask the device (the only HIP calls)
+constexpr int RESIDENT_UNUSED = -1;  // ... geometry and workspace only (no device touched)
+
+RvqPlan rvq_plan(int batch, int frames, int nq, int ncode, int resident) {
+  RvqPlan p;
+  p.ws_bytes = (long long)pt_zst_bytes(batch, frames, nq);
+  // 16 frames per chain part: fewer, longer chain parts measured fastest at T = 87 (in-step
+  // 43.1-43.5 us vs 44.2 at F = 11, 44.4-44.8 at 12; profiles/r06g_ab.txt); fewer only where
+  // the chain's LDS would not fit twice per CU (beside an expansion workgroup: slab halves and
+  // z_q accumulators)
+  auto lds_of = [&](int F) {
+    return (size_t)max(ChainLds(nq, F, ncode).total, PT_EX_FLOATS) * sizeof(float);
+  };
+  p.F = min(FU_ROWS, frames);
+  while (p.F >= 1 && lds_of(p.F) > 80 * 1024) --p.F;
+  if (p.F < 1) return p;
+  p.P = (frames + p.F - 1) / p.F;
+  p.n_fb = (frames + PT_FB - 1) / PT_FB;
+  p.wpc = p.P + (RD / FU_CB) * p.n_fb;
+  p.lds = (int)lds_of(p.F);
+  p.ws_bytes = std::max(p.ws_bytes, (long long)(zsh_bytes(batch, nq, p.P) + FU_SYNC_BYTES));
+  // the two process-wide test hooks: vrvq_rvq_path(1) and vrvq_rvq_debug_capacity
+  if (resident == RESIDENT_UNUSED || g_rvq_path == 1) return p;
+  p.resident = resident != RESIDENT_QUERY
+                   ? resident
+                   : resident_workgroups((const void*)rvq_kernels(ncode).pt, (size_t)p.lds);
+  // a launch's granule area is addressed with 32-bit byte offsets (never the binding limit at a
+  // supported shape: one clip's granules are nq P KiB)
+  const long long fit = std::max(1LL, 0x7fffffffLL / (long long)zsh_bytes(1, nq, p.P));
+  p.clips = (int)std::min<long long>(min(min(p.resident / p.wpc, g_pt_cap_limit), batch), fit);
+  if (p.clips < 1) return p;
+  p.kind = PLAN_PT;
+  p.launches = (int)(((long long)batch + p.clips - 1) / p.clips);
+  return p;
 }
 
-// The quantizer from the conv's partials: rvq_pt_kernel per group of resident clips, or -- the
-// shape does not fit (a clip longer than the resident grid) or vrvq_rvq_path(1) -- the chain and
-// the expansion as two stream-ordered launches over the same partials (zst through the
-// workspace). Both give the same outputs bit for bit.
-template <int NM>
-int launch_pt_nm(const FusedArgs& f0, int batch, int frames, int nq, const float* part,
-                 const float* imp, int64_t* codes, float* latents, float* loss_pf, float* z_q_is,
-                 float* z_q, float* mask, void* ws, size_t ws_bytes, hipStream_t st) {
-  int F = 0, P = 0, n_fb = 0;
-  size_t lds = 0;
-  const int cap = pt_capacity<NM>(frames, nq, &F, &P, &n_fb, &lds);
-  const int R = nq * RCD;
-  if (cap < 1) {
-    if (ws_bytes < pt_zst_bytes(batch, frames, nq)) return VRVQ_ERR_ARG;
-    float* zst = static_cast<float*>(ws);
-    ChainArgs a = f0.c;
-    a.part = part; a.B = batch; a.T = frames; a.nq = nq; a.NFS = 0;
-    a.imp = imp; a.codes = codes; a.latents = latents; a.loss_pf = loss_pf; a.zst = zst;
-    a.mask = mask;
-    int rc = launch_chain(a, 256 * NM, st);
+// The quantizer from the conv's partials as planned: rvq_pt_kernel per group of resident clips,
+// or -- a clip longer than the resident grid, or vrvq_rvq_path(1) -- the chain and the expansion
+// as two stream-ordered launches over the same partials (zst through the workspace). Both give
+// the same outputs bit for bit.
+int launch_pt(const FusedArgs& f0, const RvqCall& a) {
+  const RvqPlan p = rvq_plan(a.batch, a.frames, a.nq, a.ncode, RESIDENT_QUERY);
+  if (p.kind == PLAN_CHAIN_EXPAND) {
+    if (a.ws_bytes < pt_zst_bytes(a.batch, a.frames, a.nq)) return VRVQ_ERR_ARG;
+    float* zst = static_cast<float*>(a.ws);
+    ChainArgs c = f0.c;
+    c.part = a.part; c.B = a.batch; c.T = a.frames; c.nq = a.nq; c.NFS = 0;
+    c.imp = a.imp; c.codes = a.codes; c.latents = a.latents; c.loss_pf = a.loss_pf; c.zst = zst;
+    c.mask = a.mask;
+    const int rc = launch_chain(c, a.ncode, a.st);
     if (rc) return rc;
-    return launch_expand(zst, batch, RD, frames, nq, f0.w_out, f0.b_out, imp, f0.c.level, z_q_is,
-                         z_q, nullptr, st);
+    return launch_expand(ExpandArgs{zst, a.batch, RD, a.frames, a.nq, f0.w_out, f0.b_out, a.imp,
+                                    f0.c.level, nullptr, a.z_q_is, a.z_q, nullptr},
+                         a.st);
   }
-  int bc_max = min(batch, cap);
-  while (bc_max > 1 && zsh_bytes(bc_max, nq, P) > 0x7fffffffULL) --bc_max;
-  const size_t need = zsh_bytes(bc_max, nq, P);
-  const int wpc = P + (RD / FU_CB) * n_fb;
-  for (int b0 = 0; b0 < batch; b0 += bc_max) {
-    const int bc = min(bc_max, batch - b0);
+  const size_t need = zsh_bytes(p.clips, a.nq, p.P);
+  for (int b0 = 0; b0 < a.batch; b0 += p.clips) {
+    const int bc = min(p.clips, a.batch - b0);
     FusedArgs f = f0;
     FusedLaunch L;
-    if (!fused_prepare(st, need, ws, ws_bytes, &L)) return VRVQ_ERR_UNSUPPORTED;
-    fused_chunk_args(f, b0, bc, frames, nq, F, nullptr, imp, codes, latents, loss_pf, z_q_is, z_q,
-                     mask);
-    f.z = nullptr;
-    f.z_q = z_q + (size_t)b0 * RD * frames;
-    f.c.part = part + (size_t)b0 * frames * R;  // the chunk's frames within every split
-    f.c.NFS = batch * frames;                   // split stride: the call's frames
+    if (!fused_prepare(a.st, need, a.ws, a.ws_bytes, &L)) return VRVQ_ERR_UNSUPPORTED;
+    fused_chunk_args(f, a, b0, bc, p.F);
+    f.c.part = a.part + (size_t)b0 * a.frames * a.nq * RCD;  // the chunk's frames within a split
+    f.c.NFS = a.batch * a.frames;                            // split stride: the call's frames
     f.sync = L.sync;
     f.epoch = L.epoch;
     f.zsh = reinterpret_cast<unsigned long long*>(L.area);
-    f.zsh_bytes = (int)zsh_bytes(bc, nq, P);
-    f.P = P;
-    f.n_fb = n_fb;
-    const int rc = launch_timed(rvq_pt_kernel<NM>, (unsigned)(bc * wpc), lds, st, f);
+    f.zsh_bytes = (int)zsh_bytes(bc, a.nq, p.P);
+    f.P = p.P;
+    f.n_fb = p.n_fb;
+    const int rc =
+        launch_timed(rvq_kernels(a.ncode).pt, (unsigned)(bc * p.wpc), (size_t)p.lds, a.st, f);
     if (rc) return rc;
   }
   return 0;
@@ -2193,13 +2017,6 @@ extern "C" int vrvq_debug_set_fused_flags(int flags) {
   return 0;
 }
 #endif
-
-extern "C" int vrvq_rvq_project_variant(int variant) {
-  const int prev = project_variant();
-  if (variant == 2 || variant == 3) g_project_variant = variant;
-  else if (variant != 0) return VRVQ_ERR_ARG;
-  return prev;
-}
 
 extern "C" int vrvq_rvq_cross_prep(const float* w_in_t, const float* w_out, const float* b_out,
                                    int nq, int dim, int cdim, float* mcol, float* qb,
@@ -2257,7 +2074,8 @@ extern "C" int vrvq_rvq_expand(const float* zst, int batch, int dim, int frames,
   VRVQ_CHECK_ARG(zst && w_out && b_out && z_q);
   VRVQ_CHECK_ARG(batch > 0 && frames > 0 && nq > 0 && dim >= 4);
   if (cdim != RCD) return VRVQ_ERR_UNSUPPORTED;
-  return launch_expand(zst, batch, dim, frames, nq, w_out, b_out, imp, level, z_q_is, z_q, mask,
+  return launch_expand(ExpandArgs{zst, batch, dim, frames, nq, w_out, b_out, imp, level, nullptr,
+                                  z_q_is, z_q, mask},
                        as_stream(stream));
 }
 
@@ -2268,8 +2086,9 @@ extern "C" int vrvq_rvq_expand_masked(const float* zst, int batch, int dim, int 
   VRVQ_CHECK_ARG(zst && w_out && b_out && mask && z_q);
   VRVQ_CHECK_ARG(batch > 0 && frames > 0 && nq > 0 && dim >= 4);
   if (cdim != RCD) return VRVQ_ERR_UNSUPPORTED;
-  return launch_expand(zst, batch, dim, frames, nq, w_out, b_out, nullptr, 1.0f, z_q_is, z_q,
-                       nullptr, as_stream(stream), mask);
+  return launch_expand(ExpandArgs{zst, batch, dim, frames, nq, w_out, b_out, nullptr, 1.0f, mask,
+                                  z_q_is, z_q, nullptr},
+                       as_stream(stream));
 }
 
 extern "C" int vrvq_rvq_workspace(int batch, int frames, int nq, long long* bytes) {
@@ -2282,7 +2101,7 @@ extern "C" int vrvq_rvq_workspace(int batch, int frames, int nq, long long* byte
 }
 
 extern "C" int vrvq_rvq_path(int path) {
-  const int prev = rvq_path();
+  const int prev = g_rvq_path;
   if (path == 1 || path == 2) g_rvq_path = path;
   else if (path != 0) return VRVQ_ERR_ARG;
   return prev;
@@ -2372,7 +2191,7 @@ extern "C" int vrvq_rvq_encode(const float* z, int batch, int dim, int frames, i
   float* part = static_cast<float*>(workspace);
   float* zst = part + part_floats(nf, nq);
   hipStream_t st = as_stream(stream);
-  if (rvq_path() == 2 && frames <= PJ2_TC && batch <= 0x7fffffff / (2 * FU_NP)) {
+  if (g_rvq_path == 2 && frames <= PJ_TC && batch <= 0x7fffffff / (2 * FU_NP)) {
     FusedArgs f{};
     ChainArgs& c = f.c;
     c.b_in = b_in; c.qb = qb; c.mcol = mcol; c.cb = cb; c.cbf = cbf; c.c2 = c2;
@@ -2380,21 +2199,9 @@ extern "C" int vrvq_rvq_encode(const float* z, int batch, int dim, int frames, i
     f.w_in_t = w_in_t;
     f.w_out = w_out;
     f.b_out = b_out;
-    int rc = FUSED_NA;
-    const bool pj3 = project_variant() == 3;
-    const size_t wsb = (size_t)workspace_bytes;
-#define VRVQ_FUSED_CASE(NMV)                                                                    \
-  rc = pj3 ? launch_fused_nm<NMV, true>(f, batch, frames, nq, z, imp, codes, latents, loss_pf,  \
-                                        z_q_is, z_q, mask, part, wsb, st)                     \
-           : launch_fused_nm<NMV, false>(f, batch, frames, nq, z, imp, codes, latents, loss_pf, \
-                                         z_q_is, z_q, mask, part, wsb, st)
-    switch (ncode / 256) {
-      case 1: VRVQ_FUSED_CASE(1); break;
-      case 2: VRVQ_FUSED_CASE(2); break;
-      case 3: VRVQ_FUSED_CASE(3); break;
-      default: VRVQ_FUSED_CASE(4); break;
-    }
-#undef VRVQ_FUSED_CASE
+    const int rc = launch_fused(f, RvqCall{batch, frames, nq, ncode, z, nullptr, imp, codes,
+                                          latents, loss_pf, z_q_is, z_q, mask, workspace,
+                                          (size_t)workspace_bytes, st});
     if (rc != FUSED_NA) return rc;
   }
   int rc = launch_project(z, batch, frames, nq, w_in_t, part, st);
@@ -2402,8 +2209,9 @@ extern "C" int vrvq_rvq_encode(const float* z, int batch, int dim, int frames, i
   rc = vrvq_rvq_chain(part, batch, frames, nq, ncode, cdim, b_in, qb, mcol, cb, cbf, c2, imp,
                       level, codes, latents, loss_pf, zst, mask, stream);
   if (rc) return rc;
-  return launch_expand(zst, batch, dim, frames, nq, w_out, b_out, imp, level, z_q_is, z_q,
-                       nullptr, st);
+  return launch_expand(ExpandArgs{zst, batch, dim, frames, nq, w_out, b_out, imp, level, nullptr,
+                                  z_q_is, z_q, nullptr},
+                       st);
 }
 
 extern "C" int vrvq_rvq_w_in_planes_size(int nq, int dim, int cdim, long long* n_u16) {
@@ -2423,16 +2231,21 @@ extern "C" int vrvq_rvq_pack_w_in(const float* w_in_t, int nq, int dim, int cdim
   return vrvq_launch_status();
 }
 
+extern "C" int vrvq_rvq_plan(int batch, int frames, int nq, int ncode, int resident,
+                             long long out[10]) {
+  VRVQ_CHECK_ARG(out && batch > 0 && frames > 0 && nq > 0 && ncode > 0 && resident >= 0);
+  if (!rvq_shape_ok(RD, RCD, nq, ncode)) return VRVQ_ERR_UNSUPPORTED;
+  const RvqPlan p = rvq_plan(batch, frames, nq, ncode, resident);
+  const long long v[10] = {p.kind, p.F, p.P, p.n_fb, p.wpc, p.lds, p.resident, p.clips,
+                           p.launches, p.ws_bytes};
+  std::copy(v, v + 10, out);
+  return 0;
+}
+
 extern "C" int vrvq_rvq_workspace_part(int batch, int frames, int nq, int ncode, long long* bytes) {
   VRVQ_CHECK_ARG(bytes && batch > 0 && frames > 0 && nq > 0 && ncode > 0);
-  if (nq > CH_NQMAX || ncode % 256 != 0 || ncode > 1024) return VRVQ_ERR_UNSUPPORTED;
-  // the fused launch's granules under stream capture (+ its sync block), or the two-launch
-  // fallback's zst rows: the larger
-  long long g = 0;
-  const int F = pt_frames_per_part(frames, nq, ncode);
-  if (F >= 1) g = (long long)zsh_bytes(batch, nq, (frames + F - 1) / F) + (long long)FU_SYNC_BYTES;
-  const long long z = (long long)pt_zst_bytes(batch, frames, nq);
-  *bytes = g > z ? g : z;
+  if (!rvq_shape_ok(RD, RCD, nq, ncode)) return VRVQ_ERR_UNSUPPORTED;
+  *bytes = rvq_plan(batch, frames, nq, ncode, RESIDENT_UNUSED).ws_bytes;
   return 0;
 }
 
@@ -2450,52 +2263,24 @@ extern "C" int vrvq_rvq_encode_part(const float* part, int batch, int dim, int f
   VRVQ_CHECK_ARG(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)part & 15) == 0);
   if (!rvq_shape_ok(dim, cdim, nq, ncode)) return VRVQ_ERR_UNSUPPORTED;
   VRVQ_CHECK_ARG((long long)batch * frames * nq * RCD * PJ_SPLIT < 0x7fffffffLL);
-  long long need = 0;
-  const int rc0 = vrvq_rvq_workspace_part(batch, frames, nq, ncode, &need);
-  if (rc0) return rc0;
-  VRVQ_CHECK_ARG(workspace_bytes >= need);
+  VRVQ_CHECK_ARG(workspace_bytes >= rvq_plan(batch, frames, nq, ncode, RESIDENT_UNUSED).ws_bytes);
   FusedArgs f{};
   ChainArgs& c = f.c;
   c.b_in = b_in; c.qb = qb; c.mcol = mcol; c.cb = cb; c.cbf = cbf; c.c2 = c2;
   c.level = level;
   f.w_out = w_out;
   f.b_out = b_out;
-  // VRVQ_RVQ_WARM=1: the loader warms the stage tables' L2 first (A/B; measured slower here:
-  // stage 0 lands at ~6 us, profiles/r06f_ab.txt, r06c_ab.txt)
-  static const int warm = [] {
-    const char* e = getenv("VRVQ_RVQ_WARM");
-    return e ? atoi(e) : 0;
-  }();
-  f.warm = warm;
-  // the loader's two looks in flight (VRVQ_RVQ_POLL2=0: one, the A/B)
-  static const int poll2 = [] {
-    const char* e = getenv("VRVQ_RVQ_POLL2");
-    return e ? atoi(e) : 1;
-  }();
-  f.poll2 = poll2;
-  hipStream_t st = as_stream(stream);
-  const size_t wsb = (size_t)workspace_bytes;
-  switch (ncode / 256) {
-    case 1: return launch_pt_nm<1>(f, batch, frames, nq, part, imp, codes, latents, loss_pf, z_q_is, z_q, mask, workspace, wsb, st);
-    case 2: return launch_pt_nm<2>(f, batch, frames, nq, part, imp, codes, latents, loss_pf, z_q_is, z_q, mask, workspace, wsb, st);
-    case 3: return launch_pt_nm<3>(f, batch, frames, nq, part, imp, codes, latents, loss_pf, z_q_is, z_q, mask, workspace, wsb, st);
-    default: return launch_pt_nm<4>(f, batch, frames, nq, part, imp, codes, latents, loss_pf, z_q_is, z_q, mask, workspace, wsb, st);
-  }
+  return launch_pt(f, RvqCall{batch, frames, nq, ncode, nullptr, part, imp, codes, latents, loss_pf,
+                              z_q_is, z_q, mask, workspace, (size_t)workspace_bytes,
+                              as_stream(stream)});
 }
 
 extern "C" int vrvq_rvq_fused_clips(int frames, int nq, int ncode, int* clips) {
   VRVQ_CHECK_ARG(clips && frames > 0 && nq > 0);
   *clips = 0;
   if (!rvq_shape_ok(RD, RCD, nq, ncode)) return VRVQ_ERR_UNSUPPORTED;
-  int F = 0, P = 0, n_fb = 0;
-  size_t lds = 0;
-  switch (ncode / 256) {
-    case 1: *clips = pt_capacity<1>(frames, nq, &F, &P, &n_fb, &lds); break;
-    case 2: *clips = pt_capacity<2>(frames, nq, &F, &P, &n_fb, &lds); break;
-    case 3: *clips = pt_capacity<3>(frames, nq, &F, &P, &n_fb, &lds); break;
-    default: *clips = pt_capacity<4>(frames, nq, &F, &P, &n_fb, &lds); break;
-  }
-  if (*clips < 0) *clips = 0;
+  // what a call of any batch size could hold: no batch to cap it
+  *clips = rvq_plan(0x7fffffff, frames, nq, ncode, RESIDENT_QUERY).clips;
   return 0;
 }
 

@@ -933,16 +933,6 @@ std::tuple<Tensor, Tensor> unpack_codes(const Tensor& packed, const Tensor& coun
 // Backward operators of the generator (scripts/train.py:262-330), used by
 // the torch.autograd.Functions of vrvq_amd/train.py.
 
-// Strided weight gradients through the phase-split view (default) | VRVQ_WGRAD_PHASE=0: the
-// strided fp32 weight-gradient kernel.
-static bool phase_wgrad_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("VRVQ_WGRAD_PHASE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // torch.nn.grad.conv1d_weight of a Snake-fused conv (include/vrvq.h, vrvq_conv1d_wgrad).
 Tensor conv1d_wgrad(const Tensor& a, const Tensor& x, int64_t k, int64_t stride, int64_t pad,
                     int64_t dil, const optional<Tensor>& alpha_a,
@@ -967,10 +957,11 @@ Tensor conv1d_wgrad(const Tensor& a, const Tensor& x, int64_t k, int64_t stride,
   // values): the wgrad kernels would otherwise evaluate it in every row tile x chunk that
   // stages the operand (M / 64 times over for x)
   Tensor as_, xs_;
-  if (stride > 1 && (stride & (stride - 1)) == 0 && k == 2 * stride && dil == 1 &&
-      phase_wgrad_enabled()) {
-    // strided taps j = q s + r (the strided encoder convs, the ConvTranspose layers): a stride-1
-    // 2-tap product over the phase-split view xv[c s + r][m] = snake(x)[c][m s + r - pad]
+  if (stride > 1 && (stride & (stride - 1)) == 0 && k == 2 * stride && dil == 1) {
+    // strided weight gradients through the phase-split view (every other strided shape takes the
+    // strided fp32 weight-gradient kernel below). Strided taps j = q s + r (the strided encoder
+    // convs, the ConvTranspose layers): a stride-1 2-tap product over the phase-split view
+    // xv[c s + r][m] = snake(x)[c][m s + r - pad]
     // (vrvq_phase_split, Snake applied there), on the x3 weight-gradient kernel; then
     // dW[m][c][q s + r] = dW'[m][c s + r][q]
     if (alpha_a.has_value()) {

@@ -608,16 +608,6 @@ int launch_wgrad(WgradArgs w, hipStream_t st, bool x3) {
   return vrvq_launch_status();
 }
 
-// Stride-1 weight gradients on the split bf16 MFMA (wgrad_x3_kernel) unless VRVQ_WGRAD_X3=0
-// (A/B and tests: the fp32-input MFMA kernel for every shape).
-static bool wgrad_x3_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("VRVQ_WGRAD_X3");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 extern "C" int vrvq_conv1d_wgrad(const float* a, int batch, int m, int ta,
                                  const float* alpha_a, const float* inv_alpha_a, const float* x,
                                  int c, int tx, const float* alpha, const float* inv_alpha, int k,
@@ -637,8 +627,9 @@ extern "C" int vrvq_conv1d_wgrad(const float* a, int batch, int m, int ta,
     if (w.W <= WG_WMAX) break;
   }
   if (w.W > WG_WMAX) return VRVQ_ERR_UNSUPPORTED;
-  // the x3 kernel: stride 1, 64-sample chunks (window <= 64 + 7 * 9 samples)
-  const bool x3 = wgrad_x3_enabled() && stride == 1 && w.kt_sh == 6;
+  // the x3 kernel (wgrad_x3_kernel, split bf16 MFMA): stride 1, 64-sample chunks (window <= 64 +
+  // 7 * 9 samples); every other shape takes the fp32-input MFMA kernel
+  const bool x3 = stride == 1 && w.kt_sh == 6;
   w.WP = w.W | 1;
   w.chunks = batch * ((ta + (1 << w.kt_sh) - 1) >> w.kt_sh);
   if (w.n_split > w.chunks) w.n_split = w.chunks;
