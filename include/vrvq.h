@@ -561,6 +561,57 @@ int vrvq_spectral_distance(const float* est, const float* ref, int rows, int ref
                            double* terms, double* distance, void* workspace,
                            long long workspace_bytes, vrvq_stream_t stream);
 
+/* Sample-rate conversion (library version 106): julius.resample_frac as
+ * audiotools.AudioSignal.resample calls it (zeros = 24, rolloff = 0.945), which the reference runs
+ * in scripts/inference.py:187, models/dac_base.py:182 / :296 and models/discriminator.py:87. A
+ * polyphase windowed-sinc FIR; neither julius nor audiotools is available to the project, so the
+ * definition below is the specification (parity with julius itself unpinned).
+ *
+ * With g = gcd(old_sr, new_sr): old = old_sr / g, new = new_sr / g, sr = min(old, new) * rolloff,
+ * W = ceil(zeros * old / sr), K = 2 W + old. For phase i < new and tap j < K, in fp64:
+ *   u      = (-i / new + (j - W) / old) * sr,  t = clamp(u, -zeros, +zeros) * pi
+ *   k_i[j] = sinc(t) * cos(t / zeros / 2)^2    (sinc(0) = 1),   k_i /= sum_j k_i[j]
+ *   y[f new + i] = sum_j k_i[j] * x[clamp(f old + j - W, 0, L - 1)]       (replicate padding)
+ * Output length: floor(new L / old) by default, in 64-bit integers (julius rounds it through a
+ * float32 tensor; this does not), anything in [1, ceil(new L / old)] on request.
+ * Taps with |u| >= zeros carry the window's cos(pi / 2)^2, below 1e-30 of the centre tap: they are
+ * dropped. The table is [new][ntaps] fp32 (built in fp64, rounded once) with ntaps the largest
+ * number of kept taps of a phase (at most floor(2 zeros old / sr) + 1), and first[new]: row i
+ * holds taps j = first[i] .. first[i] + ntaps - 1, zero where dropped; first is non-decreasing and
+ * first[i] + ntaps <= K.
+ * Supported: old, new <= 1024 after reduction, 0 < zeros <= 1024, 0 < rolloff <= 1, L <= 2^40.
+ * Anything else: VRVQ_ERR_ARG, and vrvq_resample_error() names the reason (the reduced ratio).
+ *
+ *   vrvq_resample_plan   host only, touches no device. out = {old, new, W, K, ntaps, default
+ *                        output length of `length` samples, largest output length, new * ntaps
+ *                        (floats of the tap table; first has `new` entries)}. length >= 0.
+ *   vrvq_resample_taps   host only: fills HOST buffers taps [new][ntaps] (taps_len floats, at least
+ *                        new * ntaps) and first [new] (first_len ints, at least new).
+ *   vrvq_resample        y [rows][out_length] from x [rows][length], device memory. old, new, W,
+ *                        ntaps as the plan gives them, taps / first the table on the device. One
+ *                        workgroup owns VRVQ_RESAMPLE_TILE consecutive outputs of one row, stages
+ *                        the input window they read in LDS (the clamp applied there) and every lane
+ *                        accumulates its outputs as an fp32 fma chain over the row's ntaps taps in
+ *                        ascending j. No atomics, no host sync; a row's bits do not depend on the
+ *                        other rows or their number. rows <= 65535.
+ *   vrvq_resample_adjoint  the transpose: dx [rows][length] from dy [rows][out_length], gather
+ *                        form: dx[m] = sum over the outputs whose window covers m of k_i[j] dy[n],
+ *                        frames then phases ascending; a second one-workgroup-per-row launch adds
+ *                        the gradient of the replicated edges to dx[0] and dx[length - 1]. No
+ *                        atomics. */
+#define VRVQ_RESAMPLE_TILE 512
+int vrvq_resample_plan(int old_sr, int new_sr, int zeros, double rolloff, long long length,
+                       long long out[8]);
+int vrvq_resample_taps(int old_sr, int new_sr, int zeros, double rolloff, float* taps,
+                       long long taps_len, int* first, long long first_len);
+const char* vrvq_resample_error(void);
+int vrvq_resample(const float* x, int rows, long long length, int old_rate, int new_rate, int width,
+                  int ntaps, const float* taps, const int* first, float* y, long long out_length,
+                  vrvq_stream_t stream);
+int vrvq_resample_adjoint(const float* dy, int rows, long long out_length, int old_rate,
+                          int new_rate, int width, int ntaps, const float* taps, const int* first,
+                          float* dx, long long length, vrvq_stream_t stream);
+
 /* Variable-length code packing from importance masks (the reference's
  * DACFile, models/dac_base.py:19-58, stores the full uint16 code matrix). Packed stream is
  * clip-major, frame-major, stage-minor uint16: packed[clip_off[b] + frame_off[b,t] + i] =

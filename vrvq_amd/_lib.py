@@ -71,6 +71,13 @@ SIGNATURES = {
     "vrvq_spectral_distance": [_P, _P, _I, _I, ctypes.c_longlong, _P, _I, _P, _P, _P, _P, _P,
                                ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                _P, _P, _P, ctypes.c_longlong, _P],
+    "vrvq_resample_plan": [_I, _I, _I, ctypes.c_double, ctypes.c_longlong, _P],
+    "vrvq_resample_taps": [_I, _I, _I, ctypes.c_double, _P, ctypes.c_longlong, _P,
+                           ctypes.c_longlong],
+    "vrvq_resample": [_P, _I, ctypes.c_longlong, _I, _I, _I, _I, _P, _P, _P, ctypes.c_longlong,
+                      _P],
+    "vrvq_resample_adjoint": [_P, _I, ctypes.c_longlong, _I, _I, _I, _I, _P, _P, _P,
+                              ctypes.c_longlong, _P],
     "vrvq_pack_counts": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "vrvq_pack_codes": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "vrvq_unpack_offsets": [_P, _I, _I, _P, _P, _P],
@@ -100,10 +107,12 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_timing_read": ([_P, _P], _I), "vrvq_rvq_pending_error": ([_P], _I),
          "vrvq_rvq_debug": ([ctypes.c_uint, ctypes.c_uint], _I),
          "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I),
-         "vrvq_conv_plan": ([_I] * 11 + [_P], _I)}
+         "vrvq_conv_plan": ([_I] * 11 + [_P], _I),
+         "vrvq_resample_error": ([], ctypes.c_char_p)}
 
 METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
 SPECTRAL_TILE_SAMPLES = 8192  # VRVQ_SPECTRAL_TILE_SAMPLES (tests/test_spectral.py compares)
+RESAMPLE_TILE = 512  # VRVQ_RESAMPLE_TILE (tests/test_resample.py compares)
 
 
 def spectral_tile_frames(window: int) -> int:
@@ -242,3 +251,41 @@ def rvq_plan(batch: int, frames: int, nq: int, ncode: int = 1024, resident: int 
     out = (ctypes.c_longlong * 10)()
     call("vrvq_rvq_plan", batch, frames, nq, ncode, resident, out)
     return dict(zip(RVQ_PLAN_KEYS, (int(v) for v in out)))
+
+
+RESAMPLE_PLAN_KEYS = ("old", "new", "W", "K", "ntaps", "out_length", "out_length_max",
+                      "taps_len")
+
+
+def _resample_call(name: str, *args) -> None:
+    lib = load()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        why = lib.vrvq_resample_error() or lib.vrvq_status_string(rc)
+        raise RuntimeError(f"{name} failed ({rc}): {why.decode() if why else 'unknown'}")
+
+
+def resample_plan(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945,
+                  length: int = 0) -> dict:
+    """The reduced ratio, the filter's half-width W and length K, the kept taps per phase and the
+    output lengths of `length` input samples (include/vrvq.h vrvq_resample_plan; no GPU needed).
+    Raises RuntimeError naming the reduced ratio where it is unsupported. Keys:
+    RESAMPLE_PLAN_KEYS."""
+    out = (ctypes.c_longlong * 8)()
+    _resample_call("vrvq_resample_plan", int(old_sr), int(new_sr), int(zeros), float(rolloff),
+                   int(length), out)
+    return dict(zip(RESAMPLE_PLAN_KEYS, (int(v) for v in out)))
+
+
+def resample_taps(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945):
+    """(taps float32 (new, ntaps), first int32 (new,)) as NumPy arrays: the tap table of
+    include/vrvq.h vrvq_resample_taps, built on the host in fp64 and rounded once."""
+    import numpy as np
+
+    plan = resample_plan(old_sr, new_sr, zeros, rolloff)
+    taps = np.empty((plan["new"], plan["ntaps"]), np.float32)
+    first = np.empty((plan["new"],), np.int32)
+    _resample_call("vrvq_resample_taps", int(old_sr), int(new_sr), int(zeros), float(rolloff),
+                   taps.ctypes.data_as(ctypes.c_void_p), taps.size,
+                   first.ctypes.data_as(ctypes.c_void_p), first.size)
+    return taps, first

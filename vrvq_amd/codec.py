@@ -16,8 +16,10 @@ What the reference body does, and how it runs here:
   measurement, as audiotools does.
 * `normalize(normalize_db)` and `ensure_max_of_audio()` (peak <= 1 per channel) — elementwise
   gains on the device.
-* resampling: only the model rate is accepted (audiotools' resampler is absent); another rate
-  raises ValueError.
+* resampling (`AudioSignal.resample`, julius.resample_frac): a file at another rate is converted
+  to the model's on the device (vrvq_amd.resample, the HIP polyphase kernel) before the loudness
+  is measured, and the decoded audio is converted back to the file's rate before the crop to
+  `original_length`. With equal rates nothing runs.
 * windows: a signal no longer than `win_duration` is one window with `padding=True`; a longer
   one is zero-padded by `delay` on both sides and cut into `n_samples`-long windows (rounded up
   to a hop multiple) every `hop = get_output_length(n_samples)` samples with every encoder /
@@ -68,6 +70,17 @@ class AudioSignal:
     @property
     def device(self):
         return self.audio_data.device
+
+    def resample(self, sample_rate: int) -> "AudioSignal":
+        """To `sample_rate`, in place, returning self (audiotools.AudioSignal.resample:
+        julius.resample_frac with its defaults) on the HIP resampler, vrvq_amd.resample. The audio
+        must be on the GPU unless the rates are equal."""
+        sample_rate = int(sample_rate)
+        if sample_rate != self.sample_rate:
+            from .resampling import resample
+            self.audio_data = resample(self.audio_data, self.sample_rate, sample_rate)
+            self.sample_rate = sample_rate
+        return self
 
     @classmethod
     def load(cls, path) -> "AudioSignal":
@@ -228,13 +241,15 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
     dev = model.device
     audio = sig.audio_data.to(dev, torch.float32).clone()
     original_sr = sig.sample_rate
-    if original_sr != model.sample_rate:
-        raise ValueError(f"compress: audio at {original_sr} Hz, the model runs at "
-                         f"{model.sample_rate} Hz (resampling needs audiotools, absent)")
     original_length = audio.shape[-1]
-    input_db = loudness(audio, original_sr)
+    if original_sr != model.sample_rate:
+        # the container keeps the input's rate and length; everything below runs at the model's
+        # rate, the loudness included (models/dac_base.py:181-183)
+        from .resampling import resample
+        audio = resample(audio, original_sr, model.sample_rate)
+    input_db = loudness(audio, model.sample_rate)
     if normalize_db is not None:
-        audio = normalize(audio, original_sr, normalize_db)
+        audio = normalize(audio, model.sample_rate, normalize_db)
     audio = ensure_max_of_audio(audio)
 
     nb, nac, nt = audio.shape
@@ -357,10 +372,20 @@ def decompress(model, obj: Union[str, Path, DACFile], verbose: bool = False,
         db = torch.as_tensor(np.asarray(obj.input_db, np.float32)).reshape(-1)
         db = db.repeat_interleave(max(1, n_items // db.numel()))
         r = normalize(r, model.sample_rate, db)
-        if int(obj.sample_rate) != model.sample_rate:
-            raise ValueError("decompress: resampling needs audiotools, absent")
+        out_sr = int(obj.sample_rate)
+        if out_sr != model.sample_rate:
+            # back to the file's rate (models/dac_base.py:296-297): only the original_length
+            # samples the crop keeps are computed; an output sample does not depend on how many
+            # follow it. The decoded windows cover the resampled input, so at most the one sample
+            # the two floors can lose is missing, and is zero.
+            from .resampling import resample
+            n = r.shape[-1]
+            most = -(-out_sr * n // model.sample_rate)
+            r = resample(r, model.sample_rate, out_sr,
+                         output_length=min(int(obj.original_length), most))
+            r = torch.nn.functional.pad(r, (0, int(obj.original_length) - r.shape[-1]))
         r = r[..., :obj.original_length]
         r = r.reshape(-1, obj.channels, obj.original_length)
     finally:
         model.padding = original_padding
-    return AudioSignal(r, model.sample_rate)
+    return AudioSignal(r, out_sr)

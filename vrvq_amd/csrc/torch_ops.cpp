@@ -1240,6 +1240,56 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rvq_backward(
   return {dz, dmask, dw_in, db_in, dw_out, db_out, dcb};
 }
 
+// --------------------------------------------------------------------------- resampling
+// audiotools' AudioSignal.resample (julius.resample_frac), include/vrvq.h "Sample-rate
+// conversion": scripts/inference.py:187, models/dac_base.py:182 / :296,
+// models/discriminator.py:87. x (rows, L) -> (rows, out_length); taps (new, ntaps) float32 and
+// first (new,) int32 are vrvq_resample_taps' table on x's device, old_rate / width the plan's
+// reduced `old` and W.
+void check_resample_table(const Tensor& t, const Tensor& taps, const Tensor& first,
+                          const char* fn) {
+  check_t(t, "x");
+  check_on(taps, t, "taps");
+  check_on(first, t, "first", at::kInt);
+  TORCH_CHECK(t.dim() == 2 && t.numel() > 0, fn, ": the signal must be (rows, samples)");
+  TORCH_CHECK(taps.dim() == 2 && first.dim() == 1 && first.size(0) == taps.size(0) &&
+                  taps.numel() > 0,
+              fn, ": taps must be (new, ntaps) and first (new,)");
+}
+
+Tensor resample(const Tensor& x, const Tensor& taps, const Tensor& first, int64_t old_rate,
+                int64_t width, int64_t out_length) {
+  check_resample_table(x, taps, first, "resample");
+  c10::DeviceGuard guard(x.device());
+  const int64_t rows = x.size(0), L = x.size(1);
+  TORCH_CHECK(out_length > 0 && rows < (1LL << 31) && old_rate < (1LL << 31) &&
+                  width < (1LL << 31),
+              "resample: sizes out of range");
+  Tensor y = empty_f({rows, out_length}, x);
+  check_rc(vrvq_resample(x.data_ptr<float>(), (int)rows, L, (int)old_rate, (int)taps.size(0),
+                         (int)width, (int)taps.size(1), taps.data_ptr<float>(),
+                         first.data_ptr<int>(), y.data_ptr<float>(), out_length, stream_of(x)),
+           "vrvq_resample");
+  return y;
+}
+
+// Its transpose: dy (rows, out_length) -> dx (rows, length).
+Tensor resample_adjoint(const Tensor& dy, const Tensor& taps, const Tensor& first,
+                        int64_t old_rate, int64_t width, int64_t length) {
+  check_resample_table(dy, taps, first, "resample_adjoint");
+  c10::DeviceGuard guard(dy.device());
+  const int64_t rows = dy.size(0), out_length = dy.size(1);
+  TORCH_CHECK(length > 0 && rows < (1LL << 31) && old_rate < (1LL << 31) && width < (1LL << 31),
+              "resample_adjoint: sizes out of range");
+  Tensor dx = empty_f({rows, length}, dy);
+  check_rc(vrvq_resample_adjoint(dy.data_ptr<float>(), (int)rows, out_length, (int)old_rate,
+                                 (int)taps.size(0), (int)width, (int)taps.size(1),
+                                 taps.data_ptr<float>(), first.data_ptr<int>(),
+                                 dx.data_ptr<float>(), length, stream_of(dy)),
+           "vrvq_resample_adjoint");
+  return dx;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vrvq, m) {
@@ -1332,6 +1382,12 @@ TORCH_LIBRARY(vrvq, m) {
       "rvq_backward(Tensor dz_q, Tensor g_commit, Tensor g_codebook, Tensor z, Tensor zst, "
       "Tensor latents, Tensor codes, Tensor mask, Tensor w_in_t, Tensor w_out, Tensor b_out, "
       "Tensor mcol, Tensor cb) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def(
+      "resample(Tensor x, Tensor taps, Tensor first, int old_rate, int width, int out_length) "
+      "-> Tensor");
+  m.def(
+      "resample_adjoint(Tensor dy, Tensor taps, Tensor first, int old_rate, int width, "
+      "int length) -> Tensor");
 }
 
 #define VRVQ_IMPLS(m) \
@@ -1378,6 +1434,8 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("mask_ste_backward", &mask_ste_backward); \
   m.impl("rvq_encode_train", &rvq_encode_train); \
   m.impl("rvq_backward", &rvq_backward); \
+  m.impl("resample", &resample); \
+  m.impl("resample_adjoint", &resample_adjoint); \
 
 TORCH_LIBRARY_IMPL(vrvq, CUDA, m) { VRVQ_IMPLS(m) }
 

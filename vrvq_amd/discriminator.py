@@ -116,13 +116,14 @@ _MSD_LAYERS = [(1, 16, 15, 1, 1, 7), (16, 64, 41, 4, 4, 20), (64, 256, 41, 4, 16
 
 
 class MSD(nn.Module):
-    """Scale discriminator on the waveform resampled to sample_rate // rate (:68-98). Only
-    rate 1 (no resampling) is supported here; the reference configs use rates = []."""
+    """Scale discriminator on the waveform resampled to sample_rate // rate (:68-98) by
+    vrvq_amd.resample (the HIP polyphase kernel and its adjoint, so gradients reach the
+    generator); rate 1 resamples nothing. The reference configs use rates = []."""
 
     def __init__(self, rate: int = 1, sample_rate: int = 44100):
         super().__init__()
-        if rate != 1:
-            raise NotImplementedError("MSD resampling (rate != 1) needs audiotools' resampler")
+        if int(rate) < 1:
+            raise ValueError(f"MSD: rate must be a positive integer, got {rate}")
         self.convs = nn.ModuleList([
             _wn(nn.Conv1d(ci, co, k, s, groups=g, padding=p), True)
             for ci, co, k, s, g, p in _MSD_LAYERS])
@@ -131,6 +132,9 @@ class MSD(nn.Module):
         self.rate = rate
 
     def forward(self, x):
+        if self.rate != 1:
+            from .resampling import resample
+            x = resample(x, self.sample_rate, self.sample_rate // self.rate)
         fmap: list = []
         x = _run(self.convs, x, fmap)
         fmap.append(self.conv_post(x))

@@ -335,6 +335,20 @@ def spectral_distance(est: torch.Tensor, ref: torch.Tensor, lengths: Optional[to
                                     float(log_weight), float(mag_weight))
 
 
+def resample(x: torch.Tensor, taps: torch.Tensor, first: torch.Tensor, old_rate: int, width: int,
+             out_length: int) -> torch.Tensor:
+    """x (rows, L) -> (rows, out_length) through the polyphase tap table taps (new, ntaps) /
+    first (new,) of the reduced ratio old_rate:new with half-width `width` (include/vrvq.h
+    vrvq_resample; vrvq_amd.resample builds and caches the table)."""
+    return _ops().resample(x, taps, first, int(old_rate), int(width), int(out_length))
+
+
+def resample_adjoint(dy: torch.Tensor, taps: torch.Tensor, first: torch.Tensor, old_rate: int,
+                     width: int, length: int) -> torch.Tensor:
+    """The transpose of resample: dy (rows, out_length) -> dx (rows, length)."""
+    return _ops().resample_adjoint(dy, taps, first, int(old_rate), int(width), int(length))
+
+
 # ----------------------------------------------------------------------------- training step
 # Backward operators of the generator (include/vrvq.h "Training step"; vrvq_amd/train.py).
 def conv1d_wgrad(a, x, k: int, stride: int = 1, pad: int = 0, dil: int = 1,
@@ -561,6 +575,14 @@ def _register_fakes():
           log_weight, mag_weight):
         return (est.new_empty((est.shape[0], len(windows), 2), dtype=torch.float64),
                 est.new_empty((est.shape[0],), dtype=torch.float64))
+
+    @reg("vrvq::resample")
+    def _(x, taps, first, old_rate, width, out_length):
+        return f32(x, (x.shape[0], out_length))
+
+    @reg("vrvq::resample_adjoint")
+    def _(dy, taps, first, old_rate, width, length):
+        return f32(dy, (dy.shape[0], length))
 
     @reg("vrvq::pack_counts")
     def _(mask):
