@@ -277,24 +277,25 @@ int vrvq_rvq_frag(const float* cbn, int nq, int ncode, int cdim, float* cbf,
  * vrvq_rvq_encode is one kernel: one workgroup per clip x channel split on the bf16 matrix cores
  * with both operands split exactly into three bf16 terms (six products, fp32 accuracy). */
 
-/* Bytes of the workspace vrvq_rvq_encode needs (projection partials + straight-through rows /
- * the fused launch's stage hand-off rows, whichever is larger). */
+/* Bytes of a workspace that is enough for vrvq_rvq_encode at this shape: an upper bound kept for
+ * the ABI (since version 107 the call needs less: the projection partials, 256 batch frames nq
+ * bytes, followed by vrvq_rvq_workspace_part's bytes, and it accepts any workspace that holds
+ * those). */
 int vrvq_rvq_workspace(int batch, int frames, int nq, long long* bytes);
 
-/* RVQ launch structure (process-wide): 2 = fused launches (default): vrvq_rvq_encode runs ONE
- * fused launch where the shape allows it (frames <= 96; up to 32 clips per launch, more clips
- * run as consecutive launches), else its three launches; vrvq_rvq_encode_part runs rvq_pt_kernel
- * per group of resident clips. 1 = never fused: vrvq_rvq_encode's three launches,
- * vrvq_rvq_encode_part's two (chain, expansion): the A/B and the tests' reference. Every
- * structure gives the same outputs bit for bit. path 0 queries. Returns the previous path (1 or
- * 2), or VRVQ_ERR_ARG. */
+/* RVQ launch structure (process-wide): 2 = the fused launch (default): the quantizer runs from
+ * the projection partials as rvq_pt_kernel per group of resident clips, in vrvq_rvq_encode_part
+ * and, after its projection launch, in vrvq_rvq_encode. 1 = never fused: chain and expansion as
+ * two launches (vrvq_rvq_encode: project -> chain -> expand): the A/B and the tests' reference.
+ * Both structures give the same outputs bit for bit. path 0 queries. Returns the previous path
+ * (1 or 2), or VRVQ_ERR_ARG. */
 int vrvq_rvq_path(int path);
 
-/* The fused launches' in-kernel waits are bounded. A wait that runs out (a hang averted: it
+/* The fused launch's in-kernel waits are bounded. A wait that runs out (a hang averted: it
  * cannot happen with the whole grid resident) records a code in the stream's sync block and in
- * a host-mapped word of the process, and the workgroup POISONS its outputs (codes -1, latents /
- * z_q / z_q_is NaN) instead of passing garbage off as results. Codes: 1 a chain part's wait for
- * the projection partials, 2 an expansion wait for a stage.
+ * a host-mapped word of the process, and the workgroup POISONS its outputs (z_q / z_q_is NaN)
+ * instead of passing garbage off as results. The code is 2: an expansion workgroup's wait for a
+ * stage of the chain (1 was a wait of the kernel retired in version 107; nothing reports it).
  * vrvq_rvq_sync_error: *code = the stream's word or 0, and clears it; synchronises the stream.
  * vrvq_rvq_pending_error: *code = the process word or 0 (a timeout of any launch that has
  * completed by now), and clears it; no synchronisation -- the torch ops call it at entry and
@@ -305,8 +306,9 @@ int vrvq_rvq_sync_error(vrvq_stream_t stream, int* code);
 int vrvq_rvq_pending_error(int* code);
 int vrvq_rvq_debug(unsigned spin_max, unsigned stall);
 
-/* Kernel timing of the fused launch (bench.py's roofline): while on (process-wide), every fused
- * launch of vrvq_rvq_encode carries a pair of HIP events in its own dispatch
+/* Kernel timing of the fused launch (bench.py's roofline): while on (process-wide), every
+ * rvq_pt_kernel launch (of vrvq_rvq_encode_part and vrvq_rvq_encode; not the projection, chain
+ * or expansion launches) carries a pair of HIP events in its own dispatch
  * (hipExtLaunchKernelGGL), i.e. the kernel's duration on its stream. Returns the previous
  * setting. vrvq_rvq_timing_read waits for the recorded launches and returns the mean duration
  * (ms) and their count, then forgets them. */
@@ -348,7 +350,7 @@ int vrvq_rvq_fused_clips(int frames, int nq, int ncode, int* clips);
 int vrvq_rvq_debug_capacity(int clips);
 
 /* Debug query (library version 105): the launch plan of a vrvq_rvq_encode_part call of this
- * shape, filled by the function its launcher, vrvq_rvq_workspace_part and vrvq_rvq_fused_clips
+ * shape (and of vrvq_rvq_encode after its projection launch), filled by the function its launcher, vrvq_rvq_workspace_part and vrvq_rvq_fused_clips
  * use. resident = workgroups of rvq_pt_kernel the device holds at once; given (> 0), the query
  * is host-only and touches no device; 0 asks the current device (its occupancy query).
  * out = {kind, F (frames per chain part, <= 16), P (parts per clip), n_fb (96-frame expansion
@@ -361,17 +363,18 @@ int vrvq_rvq_plan(int batch, int frames, int nq, int ncode, int resident, long l
 
 /* The whole quantizer, the replacement of VBRResidualVectorQuantize.forward's quantizer loop,
  * importance mask and masked sum (models/quantize.py:353-365, 389-421) and of
- * ResidualVectorQuantize.forward in eval (:136-214): one fused launch (projection units, chain
- * parts that publish every stage's zst rows, expansion workgroups that write z_q_is / z_q
- * under the chain; see vrvq_rvq_path) or three stream-ordered launches (project -> chain ->
- * expand, the steps below). The fused launch hands data between its workgroups as tagged 8-byte
+ * ResidualVectorQuantize.forward in eval (:136-214), on channel-major z: the projection launch
+ * (step 1 below) writes the partials into the workspace, then the quantizer runs from them
+ * exactly as vrvq_rvq_encode_part does, at any number of frames (rvq_pt_kernel per group of
+ * resident clips; chain -> expand, steps 2 and 3, under vrvq_rvq_path(1) or for a clip longer
+ * than the resident grid). The fused launch hands data between its workgroups as tagged 8-byte
  * granules (the tag carries a per-call epoch from ONE process-wide counter, so nothing needs
  * clearing between eager calls on any stream): eager calls use a library-owned granule area
  * per (device, stream), allocated with the stream's sync block on first use (hipMalloc, outside
  * any stream capture); under stream capture the granules live in the workspace, and memsets of
- * it and of the sync block are captured in front of each launch (every replay uses epoch 1).
- * workspace: >= vrvq_rvq_workspace() bytes, 16-byte aligned, caller-owned, no initialisation
- * needed. */
+ * them and of the sync block are captured in front of each launch (every replay uses epoch 1).
+ * workspace: vrvq_rvq_workspace() bytes are always enough (see there), 16-byte aligned,
+ * caller-owned, no initialisation needed. */
 int vrvq_rvq_encode(const float* z, int batch, int dim, int frames, int nq, int ncode, int cdim,
                     const float* w_in_t, const float* b_in, const float* cb, const float* cbf,
                     const float* c2, const float* w_out, const float* b_out, const float* mcol,

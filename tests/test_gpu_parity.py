@@ -736,9 +736,10 @@ _NAMES = ("codes", "latents", "loss_pf", "z_q_is", "z_q", "mask")
 
 
 def rvq_three_entries(z, st, imp, level):
-    """The quantizer's three eval entry points on the same inputs: rvq_encode as three launches,
-    rvq_encode as the fused launch, and rvq_project's partials -> rvq_encode_part (the default
-    encode's rvq_pt_kernel). Asserts all six outputs bit-equal and returns them."""
+    """The quantizer's three eval entry points on the same inputs: rvq_encode as three launches
+    (path 1), rvq_encode as its projection launch + rvq_pt_kernel (path 2), and rvq_project's
+    partials -> rvq_encode_part (the default encode's rvq_pt_kernel). Asserts all six outputs
+    bit-equal and returns them."""
     from test_gpu_rvq_part import _part_call, _project
     from vrvq_amd import _lib
     outs = []
@@ -823,6 +824,10 @@ def test_rvq_exact_ties_take_lowest_index(pattern, nq, ncode):
 
 
 def _rvq_both_paths(nq, ncode, B, T, imp_on, zqis, seed, repeats=3, side_load=False):
+    """ops.rvq_encode on channel-major z under vrvq_rvq_path(2) (projection + rvq_pt_kernel)
+    against path 1 (project -> chain -> expand): bit-equal outputs on every repeat, no wait ran
+    out, and exactly the rvq_pt_kernel launches the plan says (none where it plans chain +
+    expand, e.g. under rvq_debug_capacity(0))."""
     from vrvq_amd import _lib
     q, gen = _random_rvq(nq, ncode, seed)
     st = q.stacked()
@@ -835,11 +840,12 @@ def _rvq_both_paths(nq, ncode, B, T, imp_on, zqis, seed, repeats=3, side_load=Fa
         want = run()
         torch.cuda.synchronize()
         _lib.rvq_path(2)
+        p = _lib.rvq_plan(B, T, nq, ncode)  # with the hooks set now (path 2, any capacity cap)
         got = []
         side = torch.cuda.Stream() if side_load else None
         a = torch.randn(2048, 2048, device=DEV) if side_load else None
         _lib.rvq_timing_read()  # forget earlier timed launches
-        _lib.rvq_timing(True)   # counts the fused launches that actually ran
+        _lib.rvq_timing(True)   # counts the rvq_pt_kernel launches that actually ran
         for r in range(repeats):
             if side is not None:  # uneven load: a GEMM stream on part of the chip meanwhile
                 side.wait_stream(torch.cuda.current_stream())
@@ -854,39 +860,53 @@ def _rvq_both_paths(nq, ncode, B, T, imp_on, zqis, seed, repeats=3, side_load=Fa
     finally:
         _lib.rvq_timing(False)
         _lib.rvq_path(prev)
-    # the fused launch ran (one per <= 32 clips) for T <= 96, none above (no silent fallback)
-    assert launched == (repeats * ((B + 31) // 32) if T <= 96 else 0), launched
+    # the launches the plan says ran, at every T (an exact count: no silent fallback)
+    assert launched == repeats * (p["launches"] if p["kind"] == _lib.RVQ_PLAN_PT else 0), launched
     names = ("codes", "latents", "loss_pf", "z_q_is", "z_q", "mask")
     for g in got:
         for name, x, y in zip(names, want, g):
             assert (x is None and y is None) or torch.equal(x, y), name
+    return launched
 
 
 @pytest.mark.parametrize("nq,ncode,B,T,imp_on,zqis", [
     (8, 1024, 32, 87, True, True),     # configs[1]: one launch of 32 clips
-    (32, 1024, 64, 87, True, True),    # configs[2]: two launches of 32 clips
-    (28, 1024, 40, 87, True, True),    # a ragged second launch
+    (32, 1024, 64, 87, True, True),    # configs[2]: the launches of the plan's resident clips
+    (28, 1024, 40, 87, True, True),    # a ragged batch
     (5, 512, 3, 40, True, True), (1, 1024, 4, 87, False, True), (9, 256, 2, 7, True, False),
     (2, 1024, 1, 1, True, True), (12, 768, 2, 96, True, True), (3, 1024, 5, 65, False, False),
-    (8, 1024, 3, 97, True, True)])     # T > 96: the three launches either way
+    (8, 1024, 3, 97, True, True)])     # T > 96: the in-launch path too (two expansion windows)
 def test_rvq_fused_bit_identical_to_three_launches(nq, ncode, B, T, imp_on, zqis):
-    """The fused RVQ launch (projection units -> chain parts that publish each stage -> the
-    expansion workgroups, in-launch hand-offs) returns every output of the three launches bit
-    for bit, on repeated calls (stale flags of the previous call never pass a wait), with chain
-    parts that have no frames (T < 8), odd nq, every codebook size and the batch split over
-    launches; no wait ran out."""
+    """rvq_encode on channel-major z as the projection launch + rvq_pt_kernel (chain parts that
+    publish each stage -> the expansion workgroups, in-launch hand-offs) returns every output of
+    the three launches bit for bit, on repeated calls (stale granules of the previous call never
+    pass a wait), with one frame, T below / at / above an expansion window, odd nq, every
+    codebook size and a ragged batch; no wait ran out."""
     _rvq_both_paths(nq, ncode, B, T, imp_on, zqis, 77 * nq + T + B)
 
 
+def test_rvq_fused_capacity_zero_takes_chain_and_expansion():
+    """With the resident-clip capacity forced to 0 (a clip too long for the grid), rvq_encode
+    on channel-major z runs project -> chain -> expand under path 2 as well: no timed
+    rvq_pt_kernel launch, and path 1's bits."""
+    from vrvq_amd import _lib
+    prev = _lib.rvq_debug_capacity(0)
+    try:
+        assert _rvq_both_paths(4, 256, 2, 40, True, True, 4 * 77 + 40 + 2) == 0
+    finally:
+        _lib.rvq_debug_capacity(prev)
+
+
 def test_rvq_fused_under_uneven_load():
-    """The fused launch while GEMMs on another stream hold part of the chip (workgroups start
-    late and unevenly): same bits as the three launches, no wait ran out."""
+    """Projection + rvq_pt_kernel while GEMMs on another stream hold part of the chip
+    (workgroups start late and unevenly): same bits as the three launches, no wait ran out."""
     _rvq_both_paths(8, 1024, 32, 87, True, True, 4242, repeats=4, side_load=True)
 
 
 def test_rvq_fused_graph_replay():
-    """Captured in a CUDA graph (a memset of the flag block is captured before the launch):
-    replays give the three launches' bits, also after eager calls on the same stream."""
+    """Captured in a CUDA graph (the projection launch, the memset nodes of the sync block and
+    the granules in the workspace, the rvq_pt_kernel launch): replays give the three launches'
+    bits, also after eager calls on the same stream."""
     from vrvq_amd import _lib
     q, gen = _random_rvq(8, 1024, 99)
     st = q.stacked()

@@ -220,8 +220,8 @@ def test_rvq_part_launch_counts():
 
 
 def test_rvq_fused_timeout_is_loud():
-    """rvq_encode's fused launch on channel-major z: a hand-off wait that runs out (waits bounded
-    at 64 polls, the first projection unit held back) poisons its outputs (codes -1 or NaN z_q)
+    """rvq_encode on channel-major z (projection launch + rvq_pt_kernel): a hand-off wait that
+    runs out (waits bounded at 64 polls, chain part 0 held back) poisons its outputs (NaN z_q)
     and the NEXT RVQ call raises RuntimeError without any synchronisation in between; after the
     knob is reset a clean call succeeds and reports nothing."""
     q, gen = _random_rvq(8, 1024, 31)

@@ -63,6 +63,24 @@ def test_workspace_and_geometry_match_parent_record():
                 (_lib.RVQ_PLAN_CHAIN_EXPAND, 0, 2), row
 
 
+def test_encode_workspace_bound_covers_partials_and_plan():
+    """vrvq_rvq_workspace keeps the parent's bytes (the `ws` column, checked above) as an upper
+    bound: vrvq_rvq_encode needs the projection partials (8 splits x B T x 8 nq floats) followed
+    by the plan's workspace, and that fits at every accepted shape of the fixture."""
+    lib = _lib.load()
+    n = ctypes.c_longlong(0)
+    accepted = 0
+    for batch, frames, nq, ncode, status_part, _ws_part, status, _ws in fixture()["host"]:
+        if status_part or status:
+            continue
+        accepted += 1
+        assert lib.vrvq_rvq_workspace(batch, frames, nq, ctypes.byref(n)) == 0
+        need = 256 * batch * frames * nq + \
+            _lib.rvq_plan(batch, frames, nq, ncode, ANY_RESIDENT)["ws_bytes"]
+        assert need <= n.value, (batch, frames, nq, ncode)
+    assert accepted > 1400
+
+
 def test_fixture_covers_the_rules():
     fx = fixture()
     assert {r[4] for r in fx["host"]} == {0, 10001, 10002}

@@ -1,5 +1,5 @@
 // Write-rate micro-benchmark for the fused RVQ expansion's z_q_is stream (csrc/rvq.hip
-// fused_expand_body): the same store pattern -- per stage i, a (clip, 128-channel block)
+// pt_expand_body's store_quad stores): the same store pattern -- per stage i, a (clip, 128-channel block)
 // workgroup of 8 waves writes its 128 x T rows of z_q_is[b][i] as 16-B quads of four frames,
 // 8 rows x 128 B per wave instruction -- with no loads, no MFMAs, no hand-off waits. Variants:
 //   wgs_per_block = 1: one 512-thread workgroup per (clip, block) (the fused launch's shape)

@@ -9,8 +9,9 @@ a wide coalesced streaming read, so the fetch bytes are doubled; WRITE_SIZE is e
 
     python tools/pmc_traffic.py gpurun_out/<tag> profiles/<tag>_rvq_pmc.json [launches per call]
 
-The path is rvq_pt_kernel (the launch from the conv's partials), rvq_fm_kernel (r05's frame-major launch) or rvq_fused_kernel where a fused launch ran (one dispatch per <= 32 clips: the
-third argument, default 1, scales a dispatch to one rvq_encode call), else the three kernels.
+The path is rvq_pt_kernel (the launch from the projection partials) or rvq_fm_kernel (r05's
+frame-major launch) where a fused launch ran (one dispatch per group of resident clips: the third
+argument, default 1, scales a dispatch to one call), else the three kernels.
 """
 import collections
 import csv
@@ -45,8 +46,6 @@ def main():
         path = ["rvq_pt_kernel"]
     elif "rvq_fm_kernel" in kernels:
         path = ["rvq_fm_kernel"]
-    elif "rvq_fused_kernel" in kernels:
-        path = ["rvq_fused_kernel"]
     else:
         path = [k for k in kernels
                 if any(s in k for s in ("rvq_project", "rvq_chain", "rvq_expand"))]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Micro-bench of the RVQ operator alone (torch.ops.vrvq.rvq_encode: project -> chain ->
-expand) at BASELINE shapes, for rocprofv3 kernel traces / PMC passes and quick timing with HIP
+"""Micro-bench of the RVQ operator alone (torch.ops.vrvq.rvq_encode on channel-major z, and
+rvq_encode_part from ready partials) at BASELINE shapes, for rocprofv3 kernel traces / PMC passes and quick timing with HIP
 events on the launch stream. Prints the median per-call time and the algorithmic HBM rate
 (bytes per SURVEY.md §8(d), the same formula as bench.py)."""
 import argparse
@@ -32,9 +32,9 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--no-zqis", action="store_true", help="want_z_q_is=False (z_q only)")
     ap.add_argument("--paths", default="pt,2,1",
-                    help="RVQ launch structures to time (pt: the launch from the conv's projection "
-                         "partials, the eval encode's; on channel-major z: 2 fused, 1 three "
-                         "launches)")
+                    help="RVQ launch structures to time (pt: rvq_pt_kernel from ready projection "
+                         "partials, the eval encode's; on channel-major z: 2 the projection "
+                         "launch + rvq_pt_kernel, 1 three launches project -> chain -> expand)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     model = vrvq_amd.DAC_VRVQ(n_codebooks=args.nq)

@@ -158,8 +158,9 @@ def call(name: str, *args) -> None:
 
 
 def rvq_path(path: int = 0) -> int:
-    """Select the RVQ launch structure (2: one fused launch where the shape allows, default; 1:
-    three launches; 0: query). Returns the previous path. Same outputs bit for bit."""
+    """Select the RVQ launch structure (2: rvq_pt_kernel from the projection partials, default;
+    1: chain and expansion as two launches; 0: query). Returns the previous path. Same outputs
+    bit for bit."""
     prev = load().vrvq_rvq_path(path)
     if prev not in (1, 2):
         raise RuntimeError(f"vrvq_rvq_path({path}) failed ({prev})")
@@ -227,8 +228,8 @@ def conv_plan(kind, batch: int, cin: int, tin: int, cout: int, k: int, stride: i
 
 
 def rvq_timing(on: bool) -> bool:
-    """Attach HIP start / stop events to every fused RVQ launch (kernel duration on its stream)
-    while on. Returns the previous setting."""
+    """Attach HIP start / stop events to every rvq_pt_kernel launch (kernel duration on its
+    stream) while on. Returns the previous setting."""
     return bool(load().vrvq_rvq_timing(1 if on else 0))
 
 
@@ -245,7 +246,8 @@ RVQ_PLAN_PT, RVQ_PLAN_CHAIN_EXPAND = 0, 1  # vrvq_rvq_plan_kind_t
 
 
 def rvq_plan(batch: int, frames: int, nq: int, ncode: int = 1024, resident: int = 0) -> dict:
-    """The launch plan of an rvq_encode_part call of this shape (include/vrvq.h vrvq_rvq_plan),
+    """The launch plan of an rvq_encode_part call of this shape, and of rvq_encode after its
+    projection launch (include/vrvq.h vrvq_rvq_plan),
     from the function that launches it. resident: workgroups of rvq_pt_kernel the device holds
     at once (given: no GPU needed; 0: ask the current device). Keys: RVQ_PLAN_KEYS."""
     out = (ctypes.c_longlong * 10)()

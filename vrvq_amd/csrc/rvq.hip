@@ -8,11 +8,12 @@
 // By linearity z_e(i) = ((P_i + b_in(i)) - Qb_i) - sum_{j<i} M_ij zst_j with P_i = W_in(i) z,
 // M_ij = W_in(i) W_out(j) (8x8) and Qb_i = W_in(i) sum_{j<i} b_out(j): the sequential part
 // lives in the 8-dim latent space and the 1024-dim work becomes two embarrassingly parallel
-// streams. The eval encode's path is ONE launch from the in_proj partials the encoder's last
-// conv computes in its epilogue (rvq_pt_kernel: chain parts + expansion workgroups that write
-// z_q_is / z_q; conv.hip vrvq_conv1d_proj); on z itself, rvq_fused_kernel (projection units,
-// chain parts and expansion in one launch for T <= 96). Both are built from the bodies of the
-// three-launch form, which stays as the reference path:
+// streams. The quantizer is ONE launch from the in_proj partials (rvq_pt_kernel: chain parts +
+// expansion workgroups that write z_q_is / z_q under the chain). The eval encode gets the
+// partials from the encoder's last conv, which computes them in its epilogue (conv.hip
+// vrvq_conv1d_proj); on channel-major z (vrvq_rvq_encode) rvq_project3_kernel writes the same
+// partials first. rvq_pt_kernel's chain parts run the body of the three-launch form, which stays
+// as the reference path:
 //
 //   rvq_project3_kernel  P partials over 8 channel splits (one workgroup per clip x 96-frame
 //                        tile x split, the z slab staged once in LDS; split-bf16 MFMA).
@@ -30,8 +31,8 @@
 // the reference's summation order, so the codes match every golden fixture BY TEST (full
 // batches included), not by construction: a near-tie could differ.
 //
-// The host side reads no environment variable. vrvq_rvq_encode_part's launch geometry (frames per
-// chain part, parts, expansion windows, LDS, clips per launch, workspace) is one RvqPlan
+// The host side reads no environment variable. The launch geometry of both entry points (frames
+// per chain part, parts, expansion windows, LDS, clips per launch, workspace) is one RvqPlan
 // (rvq_plan), shared by the launcher, vrvq_rvq_workspace_part, vrvq_rvq_fused_clips and the
 // host-only query vrvq_rvq_plan; the kernels of a codebook size come from one table (rvq_kernels).
 #include <hip/hip_ext.h>
@@ -45,7 +46,7 @@
 #include "lanes.h"
 
 #ifdef VRVQ_STAMPS
-// Fused launch (rvq_fused_kernel), diagnostic build: thread 0 of every workgroup records
+// rvq_pt_kernel, diagnostic build: thread 0 of every workgroup records
 // s_memrealtime (100 MHz, one clock for the whole chip) at its phase boundaries into
 // stamps[blockIdx][64] (tools/rvq_fused_stamps.py).
 #define FSTAMP(buf, slot)                                                                    \
@@ -165,27 +166,6 @@ __global__ void rvq_frag_kernel(const float* __restrict__ cbn, int nq, int N,
 constexpr int PJ_NT = 512;
 constexpr int PJ_TC = 96;                       // frames per tile (6 MFMA column tiles)
 
-// Where the partials go: plain stores (the three-launch path: the chain reads them after a
-// kernel boundary) or, in the fused launch, tagged 8-B granules {partial, tag} written
-// through (sc1, 16-B stores = two whole granules): the data is its own flag, the consumer
-// checks the tags of what it read (MI355X_MICROARCH.md / cdna_hip_programming.md Guideline 16,
-// R2) -- no drain, no flag word.
-struct PartSink {
-  float* part;
-  __amdgpu_buffer_rsrc_t rsrc;  // over the granule buffer (tag != 0)
-  unsigned tag;                 // 0: plain floats
-  __device__ __forceinline__ void put(size_t off, float4 v) const {
-    if (tag) {
-      const u32x4 g0 = {__float_as_uint(v.x), tag, __float_as_uint(v.y), tag};
-      const u32x4 g1 = {__float_as_uint(v.z), tag, __float_as_uint(v.w), tag};
-      __builtin_amdgcn_raw_buffer_store_b128(g0, rsrc, (int)(off * 8), 0, CPOL_SC1);
-      __builtin_amdgcn_raw_buffer_store_b128(g1, rsrc, (int)(off * 8 + 16), 0, CPOL_SC1);
-    } else {
-      *reinterpret_cast<float4*>(part + off) = v;
-    }
-  }
-};
-
 // One (clip b, frame tile tc, channel split s) projection unit on the bf16 matrix cores: both
 // operands split exactly into three bf16 terms and the six products of conv_x3.h (dropped terms
 // <= 2^-23 |ab|: fp32 accuracy) on v_mfma_f32_16x16x32_bf16 -- 2.7x the fp32 MFMA rate for the
@@ -219,10 +199,12 @@ __device__ __forceinline__ f32x4 mfma16_bf16(u32x4 a, u32x4 b, f32x4 c) {
                                                  __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-__device__ __forceinline__ void project3_body(const float* __restrict__ z, int T, int nq, int tc,
-                                              int b, int s, const float* __restrict__ w_in_t,
-                                              const PartSink& out, int NF, char* lds,
-                                              unsigned long long* stamps = nullptr) {
+__global__ __launch_bounds__(PJ_NT) void rvq_project3_kernel(const float* __restrict__ z, int T,
+                                                              int nq, int n_tc,
+                                                              const float* __restrict__ w_in_t,
+                                                              float* __restrict__ part, int NF) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tc = blockIdx.x % n_tc, b = blockIdx.x / n_tc, s = blockIdx.y;
   constexpr int NIT = (PJ_CPS / 8) * PJ_TC / PJ_NT;  // (octet, frame) items per thread: 3
   constexpr int NKS = PJ_CPS / 32;                      // K steps of 32 channels
   const int R = nq * RCD;
@@ -281,7 +263,6 @@ __device__ __forceinline__ void project3_body(const float* __restrict__ z, int T
 #pragma unroll
     for (int u = 0; u < 8; ++u) asm volatile("" ::"v"(w[ks][u]));
   __syncthreads();
-  FSTAMP(stamps, 44);
   // work items (16-row tile rt, half hf = frame tiles 3 hf .. 3 hf + 2) over the 8 waves
   for (int item = wave; item < 2 * n_rt; item += PJ_NT / 64) {
     const int rt = item >> 1, hf = item & 1;
@@ -329,20 +310,12 @@ __device__ __forceinline__ void project3_body(const float* __restrict__ z, int T
         const int t = (3 * hf + j) * 16 + lr;
         if (t < ntl) {
           const size_t n = (size_t)b * T + t0 + t;
-          out.put(((size_t)s * NF + n) * R + rr, make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]));
+          *reinterpret_cast<float4*>(part + ((size_t)s * NF + n) * R + rr) =
+              make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
         }
       }
     }
   }
-}
-
-__global__ __launch_bounds__(PJ_NT) void rvq_project3_kernel(const float* __restrict__ z, int T,
-                                                              int nq, int n_tc,
-                                                              const float* __restrict__ w_in_t,
-                                                              float* __restrict__ part, int NF) {
-  extern __shared__ __attribute__((aligned(16))) char lds3[];
-  PartSink out{part, __builtin_amdgcn_make_buffer_rsrc(part, (short)0, 0, RSRC_FLAGS), 0u};
-  project3_body(z, T, nq, blockIdx.x % n_tc, blockIdx.x / n_tc, blockIdx.y, w_in_t, out, NF, lds3);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -367,8 +340,8 @@ __global__ __launch_bounds__(PJ_NT) void rvq_project3_kernel(const float* __rest
 struct ChainArgs {
   const float* part;   // [8][NFS][nq*8]
   int B, T, nq, F, NF;
-  int NFS;             // split stride of part in frames (the three-launch path: NF; the fused
-                       // launch from the conv's partials: the frames of the whole call)
+  int NFS;             // split stride of part in frames (the three-launch path: NF;
+                       // rvq_pt_kernel: the frames of the whole call)
   const float* b_in;   // [nq][8]
   const float* qb;     // [nq][8]
   const float* mcol;   // [nq][nq][8][8]
@@ -423,12 +396,12 @@ struct ChainLds {
 };
 
 // ------------------------------------------------------------------------------------------
-// In-launch hand-offs of the fused path (rvq_fused_kernel): tagged 8-B granules {value, tag},
-// each written whole by ONE sc1 store (two per 16-B store) and read with sc1 loads; the reader
-// checks the tag of every granule it uses and re-reads until it matches, so the data is its own
-// flag (cdna_hip_programming.md Guideline 16, R2; MI355X_MICROARCH.md: granules are observed
-// untorn, also as 16-B sc1 halves). Tags: projection partials 64 epoch, stage i zst
-// 64 epoch + i + 1; epochs grow per call on a stream, so an older call's granules never match
+// The in-launch hand-off of rvq_pt_kernel (chain parts -> expansion workgroups): tagged 8-B
+// granules {value, tag}, each written whole by ONE sc1 store and read with 16-B sc1 loads (two
+// granules); the reader checks the tag of every granule it uses and re-reads until it matches,
+// so the data is its own flag -- no drain, no flag word (cdna_hip_programming.md Guideline 16,
+// R2; MI355X_MICROARCH.md: granules are observed untorn, also as 16-B sc1 halves). Stage i's zst
+// carries tag 64 epoch + i + 1; epochs grow per call, so an older call's granules never match
 // (under stream capture the granule area is zeroed by a memset node and the call uses epoch 1).
 // The sync block holds only the error word of the bounded waits.
 constexpr unsigned SPIN_MAX = 1u << 19;  // bounded spins (~0.5 s); on the bound: *err = code
@@ -436,44 +409,30 @@ constexpr unsigned SPIN_MAX = 1u << 19;  // bounded spins (~0.5 s); on the bound
 // A bounded wait that ran out (a hang averted: it cannot happen with the whole grid resident)
 // records its code in the stream's sync block (vrvq_rvq_sync_error) and in the process's
 // host-mapped error word (system scope: the host reads it without synchronising, and the next
-// vrvq_rvq_encode* call / torch op raises on it: vrvq_rvq_pending_error). The workgroup then
-// poisons its outputs (codes -1, z_q / z_q_is NaN) instead of publishing garbage as valid data.
+// vrvq_rvq_encode* call / torch op raises on it: vrvq_rvq_pending_error). The only wait is the
+// expansion's for a stage (code 2; code 1 was the retired r04 kernel's wait for its partials);
+// the workgroup then writes NaN z_q / z_q_is instead of publishing garbage as valid data.
 __device__ __forceinline__ void report_timeout(unsigned* err, unsigned* err_host, unsigned code) {
   __hip_atomic_store((gu32*)err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (err_host)
     __hip_atomic_store((gu32*)err_host, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-__device__ __forceinline__ unsigned ld_flag(const unsigned* p) {
-  return __hip_atomic_load((gu32*)(p), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_flag(unsigned* p, unsigned v) {
-  __hip_atomic_store((gu32*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-struct ChainHandoff {              // fused launches only
-  unsigned* err;
-  unsigned* err_host;              // host-mapped error word (report_timeout) or null
-  unsigned spin_max;               // bound of every wait (SPIN_MAX; smaller in the timeout test)
+struct ChainHandoff {              // rvq_pt_kernel's chain parts only
   unsigned epoch;
-  __amdgpu_buffer_rsrc_t part;     // the partials' tagged granules, read with sc1 loads
   unsigned long long* zsh;         // this part's stage-0 block of tagged zst granules
   int zsh_stage;                   // granules per stage
   unsigned long long* stamps;      // diagnostic build only
   int dbg;                         // diagnostic build only: FusedArgs::dbg
 };
 
-// Where a chain part gets pu = (P + b_in) - Qb of its frames: CH_SPLIT the 8 split partials of
-// the three-launch path (plain loads after the projection kernel), CH_GRANULE the tagged
-// partial granules of rvq_fused_kernel, CH_PART the 8 split partials the encoder's last conv wrote in its epilogue (vrvq_conv1d_proj;
-// plain loads after that kernel's boundary) in rvq_pt_kernel, which publishes every stage.
-constexpr int CH_SPLIT = 0, CH_GRANULE = 1, CH_PART = 3;
-
-template <int NM, int MODE>
+// A chain part gets pu = (P + b_in) - Qb of its frames from the 8 split partials (plain loads
+// after the kernel that wrote them: rvq_project3_kernel or the encoder's last conv,
+// vrvq_conv1d_proj). FUSED: a chain part of rvq_pt_kernel, which publishes every stage's zst to
+// the expansion workgroups of its launch; else rvq_chain_kernel, whose outputs leave at the end.
+template <int NM, bool FUSED>
 __device__ __forceinline__ void chain_body(const ChainArgs& a, float* sm, int n0, int nf,
                                            const ChainHandoff& hx) {
-  constexpr bool FUSED = MODE != CH_SPLIT;  // in-launch hand-offs: publishes every stage's zst
   constexpr int N = 256 * NM;
   constexpr int NPW = N / CH_NW;   // codes per wave
   constexpr int NT = NPW / 16;     // 16-code MFMA tiles per wave
@@ -501,8 +460,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, float* sm, int n0
   const int cw = wave * NPW;
   CSTAMP(nq, 0);
 
-  // stage 0's operands first: they do not depend on the projection (fused: the loads run
-  // under the wait for the clip's projection units)
+  // stage 0's operands first: they do not depend on the partials
   for (int e = tid; e < CH_FMAX * RCD; e += CH_NT) e_s[e] = 0.0f;
   for (int e = tid; e < CH_FMAX; e += CH_NT) e2_s[e] = 0.0f;
   float av[NT][2];  // cbn fragments of the current stage: code cw + 16 t + fl, k = 4 kh + lg
@@ -520,46 +478,10 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, float* sm, int n0
     for (int e = tid; e < R * RCD / 4; e += CH_NT)
       reinterpret_cast<float4*>(m_s)[e] = ld4(a.mcol + (size_t)e * 4);
   // ---- prologue: pu = (P + b_in) - Qb (partials summed in split order); stage 0 operands.
-  __shared__ int dead_s;  // a bounded wait ran out in this workgroup: outputs poisoned
+  // no wait is left in a chain part, so nothing sets this: it stays only so that rvq_pt_kernel
+  // compiles to the code it had with the r04 kernel beside it (its poison arm below is dead)
+  __shared__ int dead_s;
   if (tid == 0) dead_s = 0;
-  if constexpr (MODE == CH_GRANULE) {
-    // the clip's 8 partials of this part's frames: tagged granules (16-B sc1 loads, two each),
-    // each thread re-reads its item until every tag is this call's (the projection units of
-    // the clip run concurrently on other CUs); R = 8 nq: the frames' rows are contiguous
-    const unsigned ptag = hx.epoch * 64u;
-    for (int e4 = tid; e4 < nf * R / 4; e4 += CH_NT) {
-      u32x4 v[PJ_SPLIT][2];
-      for (unsigned it = 0;; ++it) {
-#pragma unroll
-        for (int sp = 0; sp < PJ_SPLIT; ++sp) {
-          const int off = (int)((((size_t)sp * a.NF + n0) * R + 4 * e4) * 8);
-          v[sp][0] = __builtin_amdgcn_raw_buffer_load_b128(hx.part, off, 0, CPOL_SC1);
-          v[sp][1] = __builtin_amdgcn_raw_buffer_load_b128(hx.part, off + 16, 0, CPOL_SC1);
-        }
-        bool ok = true;
-#pragma unroll
-        for (int sp = 0; sp < PJ_SPLIT; ++sp)
-          ok = ok && v[sp][0][1] == ptag && v[sp][0][3] == ptag && v[sp][1][1] == ptag &&
-               v[sp][1][3] == ptag;
-        if (ok) break;
-        if (it >= hx.spin_max) {
-          report_timeout(hx.err, hx.err_host, 1u);
-          dead_s = 1;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(4);
-      }
-      FSTAMP(hx.stamps, 2);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float pv = __uint_as_float(v[0][j >> 1][2 * (j & 1)]);
-#pragma unroll
-        for (int sp = 1; sp < PJ_SPLIT; ++sp) pv = pv + __uint_as_float(v[sp][j >> 1][2 * (j & 1)]);
-        const int e = 4 * e4 + j, r = e % R;
-        pu_s[e] = (pv + a.b_in[r]) - a.qb[r];
-      }
-    }
-  } else
   // Two (frame, row) items per thread per pass with all 16 partial loads in flight.
   for (int e0 = tid; e0 < nf * R; e0 += 2 * CH_NT) {
     float v[2][PJ_SPLIT];
@@ -837,7 +759,7 @@ template <int NM>
 __global__ __launch_bounds__(CH_NT) void rvq_chain_kernel(ChainArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int n0 = blockIdx.x * a.F;
-  chain_body<NM, CH_SPLIT>(a, sm, n0, min(a.F, a.NF - n0), ChainHandoff{});
+  chain_body<NM, false>(a, sm, n0, min(a.F, a.NF - n0), ChainHandoff{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -943,33 +865,20 @@ __global__ __launch_bounds__(256) void rvq_expand_kernel(ExpandArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// The fused RVQ launches: one kernel instead of projection -> chain -> expansion, every
+// The fused RVQ launch (rvq_pt_kernel, below): one kernel instead of chain -> expansion, every
 // workgroup of the grid resident at once (clips per launch from the occupancy query).
-//
-// rvq_fused_kernel (z [B][D][T], T <= 96): workgroups [0, 8 B) are (clip b, split / part s): the
-// projection unit (b, s) (project3_body, partials stored as tagged granules), then chain part s
-// of clip b (frames [s F, s F + F), F = ceil(T / 8)), which reads the clip's 8 partials of its
-// frames as they land and publishes every stage's zst.
-//
-// rvq_pt_kernel (below: from the encoder conv's projection partials, any T): workgroups
-// [0, B P) are chain parts (clip b, frames [p F, p F + F), F <= 16).
-//
-// In both, the workgroups after the chain parts are the expansion: (clip b, frame block fb,
-// 128-channel block cb) over all stages, each stage once the chain parts of its frames have
-// published it, so the z_q_is write stream runs under the chain instead of after it. Same
-// expressions as the three launches (tests/test_gpu_parity.py).
-constexpr int FU_NP = PJ_SPLIT;     // chain parts per clip of rvq_fused_kernel
+// Workgroups [0, B P) are chain parts (clip b, frames [p F, p F + F), F <= 16); the workgroups
+// after them are the expansion: (clip b, frame window fb, 128-channel block cb) over all stages,
+// each stage once the chain parts of its frames have published it, so the z_q_is write stream
+// runs under the chain instead of after it. Same expressions as the three launches
+// (tests/test_gpu_parity.py).
 constexpr int FU_ROWS = 16;         // frames per part block of the stage hand-off rows (F <= 16)
 constexpr int FU_CB = 128;          // channels per expansion workgroup
-constexpr int FU_FB = 128;          // frames per expansion workgroup
-constexpr int SYNC_ERR = 2048;      // the error word (1 partials wait, 2 stage wait)
+constexpr int SYNC_ERR = 2048;      // the error word (2: an expansion's wait for a stage ran out)
 constexpr int SYNC_WORDS = 2052;    // used words (x 4 = 8208 B, a multiple of 16)
-constexpr int FU_CLIPS_MAX = 32;    // clips per rvq_fused_kernel launch
 
 struct FusedArgs {
-  ChainArgs c;                      // part (workspace), B, T, nq, F, NF; outputs
-  const float* z;                   // [B][D][T] (rvq_fused_kernel)
-  const float* w_in_t;
+  ChainArgs c;                      // part, B, T, nq, F, NF; outputs
   const float* w_out;               // [nq][D][8]
   const float* b_out;               // [nq][D]
   float* z_q_is;                    // [B][nq][D][T] or null
@@ -988,33 +897,6 @@ struct FusedArgs {
                                     // bit 1 = chain parts skip the next stage's codebook
                                     // fragment loads (outputs wrong; timing only)
 };
-
-// Expansion workgroup (clip b, frames [128 fb, +128), channels [128 cb, +128)): wave w =
-// 32-channel tile (w & 3) x 32-frame tiles {w >> 2, (w >> 2) + 2} of the block; per stage four
-// v_mfma_f32_32x32x2_f32 per tile, D[channel][frame] = sum_k W_out[channel][k] zst[frame][k]
-// (rvq_expand_kernel's k-ordered products). D leaves the MFMA with one frame per lane and four
-// consecutive channels per register quad; a 4 x 4 transpose inside each lane quad (two DPP
-// quad_perm exchanges) turns that into four consecutive FRAMES of one channel per register
-// quad, so z_q_is / z_q leave as 16-B stores that cover 8 whole 128-B row segments per wave
-// instruction (r04's 4-B stores needed 4x the instructions; 16-B stores straight from the
-// frame-major D orientation touched 32 rows per instruction and ran slower still:
-// profiles/r05i_stamps.log). Bias and mask are then per register (the three-launch kernel's
-// expressions, per element).
-// The stage's zst rows are tagged granules (the chain's S2 stores). The workgroup reads its
-// 128-frame window of them ONCE per stage, 16 B per lane, into an LDS slab (double-buffered,
-// one barrier per stage) that every wave takes its B operands from -- r05k's waves each read
-// the rows of their own tiles, 4x the workgroup's sc1 reads. A lane loads its slice of stage
-// i + 1 (and its W_out row / biases) speculatively BEFORE stage i's stores and checks the tags
-// when it gets there -- vmcnt retires in order, so a load issued after the stores would wait
-// for them to drain (profiles/r04d_fused_timeline.txt). Slices whose tags are not this call's
-// stage yet are re-read until they are (bounded; on the bound the outputs are NaN).
-// What bounds a stage is the z_q_is write stream (11.4 MB per stage at B = 32); the same store
-// pattern alone writes at 4-5.7 TB/s (tools/micro/expand_writes.hip), next to the chain ~2.7.
-struct ExOps {
-  float4 w0, w1;
-  float bb[4];    // b_out of the lane's four output channels (one per register quad)
-};
-constexpr int FU_EX_LDS = 2 * FU_FB * RCD * 4;  // the zst slab, two stages
 
 // 4 x 4 transpose inside each lane quad: lane 4 g + k, register 4 qd + u holds E(u, k) on
 // entry and E(k, u) on exit (E(row, column) of the quad's 4 x 4 block). Two butterfly steps,
@@ -1083,161 +965,8 @@ __device__ __forceinline__ void store_quad(float* row, int t, int T, float v0, f
   }
 }
 
-__device__ __forceinline__ void fused_expand_body(const FusedArgs& f, int e, float* sm) {
-  const int nq = f.c.nq, T = f.c.T, F = f.c.F;
-  constexpr int NCB = RD / FU_CB;
-  const int cb = e % NCB;
-  const int fb = (e / NCB) % f.n_fb;
-  const int b = e / (NCB * f.n_fb);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c0 = cb * FU_CB + (wave & 3) * 32;
-  const int col = lane & 31, h = lane >> 5;
-  const int n_ft = (min(FU_FB, T - fb * FU_FB) + 31) / 32;  // frame tiles of this block
-  const int ft0 = wave >> 2;
-  const bool one = ft0 < n_ft;       // wave-uniform: the wave has a first tile
-  const bool two = ft0 + 2 < n_ft;   // ... and a second
-  const __amdgpu_buffer_rsrc_t zr =
-      __builtin_amdgcn_make_buffer_rsrc(f.zsh, (short)0, f.zsh_bytes, RSRC_FLAGS);
-  // after the transpose: lane (g = col >> 2, k = lane & 3, h), register 4 qd + u holds channel
-  // c0 + 8 qd + 4 h + k, frame tile_base + 4 g + u
-  const int chk = c0 + 4 * h + (lane & 3);  // + 8 qd
-  // the slab window: 128 frames from wlo (the last block's window ends at the clip's last frame,
-  // so it holds the moved-back last tile); lane tid loads frame wlo + (tid >> 2), dims
-  // 2 (tid & 3) + {0, 1} (frames past the clip re-read its last one: loaded, never used)
-  const int wlo = T >= FU_FB ? min(fb * FU_FB, T - FU_FB) : 0;
-  const int fi = tid >> 2, dp = tid & 3;
-  int soff;
-  {
-    const int t = min(wlo + fi, T - 1);
-    const int p = t / F, fr = t - p * F;
-    soff = ((((b * nq) * f.P + p) * FU_ROWS + fr) * RCD + 2 * dp) * 8;
-  }
-  int trow[2];    // the lane's B-operand frame (col) as a slab row
-  int tq[2];      // first of the lane's four output frames
-  unsigned nact[2];  // per output frame u: the number of active stages (mask = i < n), bytes
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int tb = tile_first_frame(fb * FU_FB + (ft0 + 2 * j) * 32, T);
-    trow[j] = min(tb - wlo + col, FU_FB - 1);
-    tq[j] = tb + 4 * (col >> 2);
-    nact[j] = active_stages4(f.c, b, tq[j]);
-  }
-  const int zstage = f.P * FU_ROWS * RCD * 8;  // bytes per stage
-  const float* wp = f.w_out + (size_t)(c0 + col) * RCD;  // A operand: channel row c0 + col
-  const size_t wstride = (size_t)RD * RCD;
-  const unsigned base = f.epoch * 64u;
-  auto load_s = [&](int i) {
-    return __builtin_amdgcn_raw_buffer_load_b128(zr, soff + i * zstage, 0, CPOL_SC1);
-  };
-  auto load = [&](int i, ExOps& o) {
-    o.w0 = ld4(wp + i * wstride);
-    o.w1 = ld4(wp + i * wstride + 4);
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) o.bb[qd] = f.b_out[(size_t)i * RD + chk + 8 * qd];
-  };
-  auto late = [&](const u32x4& g, int i) -> bool {  // wave-uniform: a slice is not stage i's
-    const unsigned tag = base + (unsigned)i + 1u;
-    return __builtin_amdgcn_ballot_w64(!(g[1] == tag && g[3] == tag)) != 0;
-  };
-  f32x16 zq[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zq[j][r] = 0.0f;
-  __shared__ int xdead_s;  // some wave's wait ran out (then no wave waits any more)
-  if (tid == 0) xdead_s = 0;
-  __syncthreads();
-  bool dead = false;       // a wait ran out: no more waits (err recorded), outputs NaN
-  u32x4 g = load_s(0);
-  ExOps cur;
-  load(0, cur);
-  for (int i = 0; i < nq; ++i) {
-    if (!dead && late(g, i)) {
-      // stage 0 lands after the chain's first stage: long sleeps between looks
-      for (unsigned it = 0;; ++it) {
-        if (it >= f.spin_max) {
-          if (lane == 0) report_timeout(f.sync + SYNC_ERR, f.err_host, 2u);
-          xdead_s = 1;
-          dead = true;
-          break;
-        }
-        if (i == 0) __builtin_amdgcn_s_sleep(16); else __builtin_amdgcn_s_sleep(4);
-        g = load_s(i);
-        if (!late(g, i)) break;
-      }
-    }
-    if (i < 8) FSTAMP(f.stamps, 56 + i);  // the stage's slice seen (diagnostic build)
-    float* slab = sm + (i & 1) * (FU_FB * RCD);
-    *reinterpret_cast<float2*>(slab + fi * RCD + 2 * dp) =
-        make_float2(__uint_as_float(g[0]), __uint_as_float(g[2]));
-    __syncthreads();  // the stage's slab is whole; the other buffer is free (stage i - 1 done)
-    dead = xdead_s != 0;
-    FSTAMP(f.stamps, 1 + i);
-    // the next stage's operands ahead of this stage's stores (unconditional, clamped stage: a
-    // branch around loads makes the waitcnt pass drain at the join)
-    g = load_s(min(i + 1, nq - 1));
-    ExOps nxt;
-    load(min(i + 1, nq - 1), nxt);
-    const float wa[4] = {h ? cur.w0.y : cur.w0.x, h ? cur.w0.w : cur.w0.z,
-                         h ? cur.w1.y : cur.w1.x, h ? cur.w1.w : cur.w1.z};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (!(j == 0 ? one : two)) break;
-      const float4 zb = *reinterpret_cast<const float4*>(slab + trow[j] * RCD + 4 * h);
-      f32x16 q;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) q[r] = 0.0f;
-#ifdef VRVQ_STAMPS
-      if (!(f.dbg & 1)) {
-#endif
-      q = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[0], zb.x, q, 0, 0, 0);
-      q = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[1], zb.y, q, 0, 0, 0);
-      q = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[2], zb.z, q, 0, 0, 0);
-      q = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[3], zb.w, q, 0, 0, 0);
-#ifdef VRVQ_STAMPS
-      }
-#endif
-      quad_transpose(q, lane);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) q[r] = dead ? __builtin_nanf("") : q[r] + cur.bb[r >> 2];
-      if (f.z_q_is) {
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-          float* row = f.z_q_is + (((size_t)b * nq + i) * RD + chk + 8 * qd) * T;
-          store_quad(row, tq[j], T, q[4 * qd], q[4 * qd + 1], q[4 * qd + 2], q[4 * qd + 3]);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned n = (nact[j] >> (8 * (r & 3))) & 0xffu;
-        const float m = (unsigned)i < n ? 1.0f : 0.0f;  // models/utils.py:45-61
-        zq[j][r] = zq[j][r] + q[r] * m;
-      }
-    }
-    if (i < 8) FSTAMP(f.stamps, 48 + i);  // the stage's stores issued (diagnostic build)
-    cur = nxt;
-  }
-  FSTAMP(f.stamps, 40);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    if (!(j == 0 ? one : two)) break;
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      float* row = f.z_q + ((size_t)b * RD + chk + 8 * qd) * T;
-      const float d = dead ? __builtin_nanf("") : 0.0f;
-      store_quad(row, tq[j], T, zq[j][4 * qd] + d, zq[j][4 * qd + 1] + d, zq[j][4 * qd + 2] + d,
-                 zq[j][4 * qd + 3] + d);
-    }
-  }
-}
-
 __device__ __forceinline__ ChainHandoff fused_handoff(const FusedArgs& f, int b, int p) {
   ChainHandoff hx;
-  hx.err = f.sync + SYNC_ERR;
-  hx.err_host = f.err_host;
-  hx.spin_max = f.spin_max;
   hx.epoch = f.epoch;
   hx.zsh = f.zsh + (size_t)(b * f.c.nq * f.P + p) * FU_ROWS * RCD;
   hx.zsh_stage = f.P * FU_ROWS * RCD;
@@ -1246,58 +975,36 @@ __device__ __forceinline__ ChainHandoff fused_handoff(const FusedArgs& f, int b,
   return hx;
 }
 
-template <int NM>
-__global__ __launch_bounds__(CH_NT, 4) void rvq_fused_kernel(FusedArgs f) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int B = f.c.B, T = f.c.T, nq = f.c.nq, F = f.c.F;
-  const int blk = blockIdx.x;
-  FSTAMP(f.stamps, 0);
-  if (blk >= B * FU_NP) {
-    fused_expand_body(f, blk - B * FU_NP, sm);
-    FSTAMP(f.stamps, 41);
-    return;
-  }
-  const int b = blk / FU_NP, s = blk - b * FU_NP;
-  const int R = nq * RCD;
-  float* part = const_cast<float*>(f.c.part);  // the workspace this launch writes (granules)
-  const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc(
-      part, (short)0, (int)((size_t)PJ_SPLIT * f.c.NF * R * 8), RSRC_FLAGS);
-  // projection unit (b, s): partials as tagged granules, then straight on to the chain
-  PartSink out{part, pr, f.epoch * 64u};
-  if (f.stall && blk == 0)  // test knob (vrvq_rvq_debug_stall): a late producer
-    for (unsigned k = 0; k < f.stall; ++k) __builtin_amdgcn_s_sleep(127);
-  project3_body(f.z, T, nq, 0, b, s, f.w_in_t, out, f.c.NF, reinterpret_cast<char*>(sm),
-                f.stamps);
-  FSTAMP(f.stamps, 45);
-  __syncthreads();  // the slab's LDS is the chain's from here
-  // chain part s of clip b
-  const int nf = min(F, T - s * F);
-  if (nf <= 0) return;  // no frames (T < 8 F): no expansion lane reads this part's block
-  ChainHandoff hx = fused_handoff(f, b, s);
-  hx.part = pr;
-  chain_body<NM, CH_GRANULE>(f.c, sm, b * T + s * F, nf, hx);
-}
-
 // W_in planes of vrvq_conv1d_proj's projection epilogue (conv_core.h proj_epilogue): 16-row
 // tiles of the R = 8 nq stage rows
 __host__ __device__ inline int pj_nrt(int nq) { return (nq * RCD + 15) / 16; }
 
 // ------------------------------------------------------------------------------------------
-// rvq_pt_kernel: the quantizer from the projection partials that the encoder's last conv wrote
-// in its epilogue (vrvq_conv1d_proj: part[8][B T][8 nq], rvq_project3_kernel's values bit for
-// bit). Neither z nor W_in is read here, and no projection sits in front of the chain.
+// rvq_pt_kernel: the quantizer from the projection partials part[8][B T][8 nq] that an earlier
+// kernel wrote: the encoder's last conv in its epilogue (vrvq_conv1d_proj) or
+// rvq_project3_kernel, the same values bit for bit. Neither z nor W_in is read here.
 //   Workgroups [0, B P): chain parts (clip b, frames [p F, p F + F), F <= 16): the 8 partials
-// of their frames (plain loads: the conv kernel's boundary orders them) summed in split order
+// of their frames (plain loads: the writer's kernel boundary orders them) summed in split order
 // -- the three-launch chain's expression, so every output equals the three-launch path's bit
 // for bit -- then the chain, publishing every stage's zst as tagged granules.
 //   Workgroups after: expansion (clip b, 96-frame window fb, 128-channel block cb), 8 waves,
-// z_q_is and the masked z_q of the window's 4 x 3 (32-channel, 32-frame) tiles with
-// fused_expand_body's expressions (four v_mfma_f32_32x32x2_f32 per tile, DPP quad transpose,
-// 16-B stores of four frames of one channel), one channel tile ct = w & 3 per wave (waves w and
-// w + 4 share a SIMD: 3 tiles per SIMD): waves 0-2 frame tiles {0, 2}, wave 3 {0, 1}, waves 4-6
-// {1}, wave 7 {2}. Wave 7 is also the LOADER: per stage it polls the window's zst granules (6 x
-// 16 B per lane, tag-checked, bounded) into one half of a double-buffered LDS slab while every
-// wave runs the previous stage out of the other half; one barrier per stage. It issues the poll
+// z_q_is and the masked z_q of the window's 4 x 3 (32-channel, 32-frame) tiles: per stage and
+// tile four v_mfma_f32_32x32x2_f32, D[channel][frame] = sum_k W_out[channel][k] zst[frame][k]
+// (rvq_expand_kernel's k-ordered products). D leaves the MFMA with one frame per lane and four
+// consecutive channels per register quad; a 4 x 4 transpose inside each lane quad (two DPP
+// quad_perm exchanges) turns that into four consecutive FRAMES of one channel per register
+// quad, so z_q_is / z_q leave as 16-B stores that cover 8 whole 128-B row segments per wave
+// instruction (4-B stores needed 4x the instructions; 16-B stores straight from the frame-major
+// D orientation touched 32 rows per instruction and ran slower still:
+// profiles/r05i_stamps.log). Bias and mask are then per register (the three-launch kernel's
+// expressions, per element). What bounds a stage is the z_q_is write stream (11.4 MB per stage
+// at B = 32); the same store pattern alone writes at 4-5.7 TB/s (tools/micro/expand_writes.hip),
+// next to the chain ~2.7.
+//   One channel tile ct = w & 3 per wave (waves w and w + 4 share a SIMD: 3 tiles per SIMD):
+// waves 0-2 frame tiles {0, 2}, wave 3 {0, 1}, waves 4-6 {1}, wave 7 {2}. Wave 7 is also the
+// LOADER: per stage it polls the window's zst granules (6 x 16 B per lane, tag-checked, bounded)
+// into one half of a double-buffered LDS slab while every wave runs the previous stage out of
+// the other half; one barrier per stage (on the bound the outputs are NaN). It issues the poll
 // BEFORE its own tile's stores and checks the tags after them: vmcnt retires in order, so the
 // check waits for the poll only, not for the stores. r05's expansion polled from every wave,
 // and where a look came too early its second look waited behind the wave's whole stage of stores
@@ -1538,25 +1245,23 @@ __global__ __launch_bounds__(CH_NT, 4) void rvq_pt_kernel(FusedArgs f) {
   const int t0 = p * F, nf = min(F, T - t0);
   if (f.stall && blk == 0)  // test knob (vrvq_rvq_debug_stall): a late producer
     for (unsigned k = 0; k < f.stall; ++k) __builtin_amdgcn_s_sleep(127);
-  chain_body<NM, CH_PART>(f.c, sm, b * T + t0, nf, fused_handoff(f, b, p));
+  chain_body<NM, true>(f.c, sm, b * T + t0, nf, fused_handoff(f, b, p));
 }
 
 // ------------------------------------------------------------------------------------------
-// Host side. The codebook size (NM = ncode / 256) is a template parameter of the three kernels
+// Host side. The codebook size (NM = ncode / 256) is a template parameter of the two kernels
 // that scan a codebook and of nothing on the host: one table, indexed by the size
 // (rvq_shape_ok: 256, 512, 768 or 1024 codes).
 struct RvqKernels {
   void (*chain)(ChainArgs);
-  void (*fused)(FusedArgs);
   void (*pt)(FusedArgs);
 };
 
 const RvqKernels& rvq_kernels(int ncode) {
-  static const RvqKernels table[4] = {
-      {rvq_chain_kernel<1>, rvq_fused_kernel<1>, rvq_pt_kernel<1>},
-      {rvq_chain_kernel<2>, rvq_fused_kernel<2>, rvq_pt_kernel<2>},
-      {rvq_chain_kernel<3>, rvq_fused_kernel<3>, rvq_pt_kernel<3>},
-      {rvq_chain_kernel<4>, rvq_fused_kernel<4>, rvq_pt_kernel<4>}};
+  static const RvqKernels table[4] = {{rvq_chain_kernel<1>, rvq_pt_kernel<1>},
+                                      {rvq_chain_kernel<2>, rvq_pt_kernel<2>},
+                                      {rvq_chain_kernel<3>, rvq_pt_kernel<3>},
+                                      {rvq_chain_kernel<4>, rvq_pt_kernel<4>}};
   return table[ncode / 256 - 1];
 }
 
@@ -1619,19 +1324,12 @@ bool rvq_shape_ok(int dim, int cdim, int nq, int ncode) {
          ncode <= 1024;
 }
 
-size_t part_floats(long long nf, int nq) { return (size_t)PJ_SPLIT * nf * nq * RCD; }
-
-// zst rows of the three-launch path ([B][nq][T][8] floats) or the fused path's tagged stage
-// granules ([B][nq][FU_NP][FU_ROWS][8] x 8 B): the workspace holds the larger
-size_t zst_floats(int batch, int frames, int nq) {
-  const size_t a = (size_t)batch * frames * nq * RCD;
-  const size_t b = (size_t)batch * nq * FU_NP * FU_ROWS * RCD * 2;
-  return a > b ? a : b;
-}
+// bytes of the projection partials [8][nf][nq 8] (a multiple of 256)
+size_t part_bytes(long long nf, int nq) { return (size_t)PJ_SPLIT * nf * nq * RCD * sizeof(float); }
 
 // ---- fused path, host side -----------------------------------------------------------------
-// 1: three launches everywhere (vrvq_rvq_path(1), the A/B and the tests' reference); 2: the
-// fused launch where the shape allows (default).
+// 1: chain and expansion as two launches everywhere (vrvq_rvq_path(1), the A/B and the tests'
+// reference); 2: rvq_pt_kernel where the plan allows (default).
 int g_rvq_path = 2;
 
 // Process-wide state of the fused launches' in-launch hand-offs:
@@ -1645,8 +1343,8 @@ int g_rvq_path = 2;
 //    caller workspace whose previous contents happened to hold 64 * epoch in a tag slot (small
 //    integer data does) could otherwise pass a check before the real granule lands.
 //  * under stream capture there is no allocation: the call uses the caller's workspace,
-//    zeroed by captured memset nodes, and epoch 1 (eager epochs start at 2); the sync block of
-//    the stream must exist from an earlier eager call, else the call takes the three launches.
+//    (sync block, then granules) zeroed by captured memset nodes, and epoch 1 (eager epochs
+//    start at 2).
 //  * the error word: a per-stream device word (vrvq_rvq_sync_error, synchronising) and one
 //    host-mapped word of the process (vrvq_rvq_pending_error, no synchronisation; the torch
 //    ops raise on it at their next call).
@@ -1672,7 +1370,7 @@ struct FusedLaunch {
 };
 
 // Sync block, epoch and granule area for one fused launch of `bytes` granules on st; false:
-// the fused launch cannot run now (the caller takes another path).
+// the fused launch cannot run (an allocation failed, or a captured call's workspace is too small).
 constexpr size_t FU_SYNC_BYTES = (SYNC_WORDS * sizeof(unsigned) + 255) & ~size_t(255);
 bool fused_prepare(hipStream_t st, size_t bytes, void* caller_ws, size_t caller_bytes,
                    FusedLaunch* L) {
@@ -1762,8 +1460,6 @@ int resident_workgroups(const void* kern, size_t lds) {
   return cache[key] = cus * per;
 }
 
-constexpr int FUSED_NA = -1;  // the fused launch does not apply: take the three launches
-
 // Launch timing (vrvq_rvq_timing): while on, every fused launch carries a (start, stop) pair of
 // HIP events in its own dispatch packet (hipExtLaunchKernelGGL), so the elapsed time is the
 // kernel's own duration on its stream (what rocprofv3 reports for it), with no marker packets
@@ -1799,12 +1495,11 @@ int launch_timed(K kern, unsigned grid, size_t lds, hipStream_t st, const FusedA
   return vrvq_launch_status();
 }
 
-// The per-call arguments of vrvq_rvq_encode / vrvq_rvq_encode_part (whole batch); the weight
-// tables travel in a FusedArgs the entry point fills once.
+// The per-call arguments of launch_pt (whole batch); the weight tables travel in a FusedArgs the
+// entry point fills once (rvq_weights).
 struct RvqCall {
   int batch, frames, nq, ncode;
-  const float* z;     // [B][D][T] (vrvq_rvq_encode) or null
-  const float* part;  // [8][B T][nq 8] (vrvq_rvq_encode_part) or null
+  const float* part;  // [8][B T][nq 8]
   const float* imp;   // or null
   int64_t* codes;
   float* latents;
@@ -1833,7 +1528,6 @@ void fused_chunk_args(FusedArgs& f, const RvqCall& a, int b0, int bc, int F) {
   c.zst = nullptr;
   c.mask = a.mask ? a.mask + b0 * nq * T : nullptr;
   c.stamps = nullptr;
-  f.z = a.z ? a.z + b0 * DT : nullptr;
   f.z_q_is = a.z_q_is ? a.z_q_is + b0 * nq * DT : nullptr;
   f.z_q = a.z_q + b0 * DT;
   f.err_host = g_err_host_dev;
@@ -1846,45 +1540,9 @@ void fused_chunk_args(FusedArgs& f, const RvqCall& a, int b0, int bc, int F) {
 size_t zsh_bytes(int bc, int nq, int P) { return (size_t)bc * nq * P * FU_ROWS * RCD * 8; }
 size_t pt_zst_bytes(int batch, int frames, int nq) { return (size_t)batch * nq * frames * RCD * 4; }
 
-// vrvq_rvq_encode's fused launch (rvq_fused_kernel, frames <= 96), <= 32 resident clips per
-// launch; FUSED_NA where it does not apply.
-int launch_fused(const FusedArgs& f0, const RvqCall& a) {
-  const int F = (a.frames + FU_NP - 1) / FU_NP;
-  size_t lds = (size_t)ChainLds(a.nq, F, a.ncode).total * sizeof(float);
-  if (lds < (size_t)PJ3_LDS) lds = PJ3_LDS;
-  if (lds < (size_t)FU_EX_LDS) lds = FU_EX_LDS;
-  if (lds > 80 * 1024) return FUSED_NA;
-  const auto kern = rvq_kernels(a.ncode).fused;
-  const int cap = min(FU_CLIPS_MAX, resident_workgroups((const void*)kern, lds) / (2 * FU_NP));
-  if (cap < 1) return FUSED_NA;
-  const int bc_max = min(a.batch, cap);
-  const size_t part_b = 2 * part_floats((long long)bc_max * a.frames, a.nq) * sizeof(float);
-  const size_t need = part_b + zsh_bytes(bc_max, a.nq, FU_NP);
-  for (int b0 = 0; b0 < a.batch; b0 += bc_max) {
-    const int bc = min(bc_max, a.batch - b0);
-    FusedArgs f = f0;
-    FusedLaunch L;
-    if (!fused_prepare(a.st, need, a.ws, a.ws_bytes, &L)) {
-      if (b0 == 0) return FUSED_NA;
-      return VRVQ_ERR_UNSUPPORTED;  // cannot happen after a first successful chunk
-    }
-    fused_chunk_args(f, a, b0, bc, F);
-    f.sync = L.sync;
-    f.epoch = L.epoch;
-    f.c.part = reinterpret_cast<float*>(L.area);  // tagged granules: 2 floats per partial
-    f.zsh = reinterpret_cast<unsigned long long*>(L.area + part_b);
-    f.zsh_bytes = (int)zsh_bytes(bc, a.nq, FU_NP);
-    f.P = FU_NP;
-    f.n_fb = 1;
-    const int rc = launch_timed(kern, (unsigned)(2 * bc * FU_NP), lds, a.st, f);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-// The launch plan of vrvq_rvq_encode_part: everything its launcher, its workspace size
-// (vrvq_rvq_workspace_part) and the queries (vrvq_rvq_fused_clips, vrvq_rvq_plan) need to agree
-// on, worked out here and nowhere else.
+// The launch plan of the quantizer from partials (vrvq_rvq_encode_part, and vrvq_rvq_encode after
+// its projection): everything the launcher, the workspace size (vrvq_rvq_workspace_part) and the
+// queries (vrvq_rvq_fused_clips, vrvq_rvq_plan) need to agree on, worked out here and nowhere else.
 enum { PLAN_PT = VRVQ_RVQ_PLAN_PT, PLAN_CHAIN_EXPAND = VRVQ_RVQ_PLAN_CHAIN_EXPAND };
 struct RvqPlan {
   int kind = PLAN_CHAIN_EXPAND;  // rvq_pt_kernel per group of resident clips | chain, then expand
@@ -1934,7 +1592,20 @@ RvqPlan rvq_plan(int batch, int frames, int nq, int ncode, int resident) {
   return p;
 }
 
-// The quantizer from the conv's partials as planned: rvq_pt_kernel per group of resident clips,
+// The weight tables of a call, as launch_pt takes them (the per-launch fields are filled there).
+FusedArgs rvq_weights(const float* b_in, const float* cb, const float* cbf, const float* c2,
+                      const float* w_out, const float* b_out, const float* mcol, const float* qb,
+                      float level) {
+  FusedArgs f{};
+  ChainArgs& c = f.c;
+  c.b_in = b_in; c.qb = qb; c.mcol = mcol; c.cb = cb; c.cbf = cbf; c.c2 = c2;
+  c.level = level;
+  f.w_out = w_out;
+  f.b_out = b_out;
+  return f;
+}
+
+// The quantizer from the partials as planned: rvq_pt_kernel per group of resident clips,
 // or -- a clip longer than the resident grid, or vrvq_rvq_path(1) -- the chain and the expansion
 // as two stream-ordered launches over the same partials (zst through the workspace). Both give
 // the same outputs bit for bit.
@@ -2093,10 +1764,14 @@ extern "C" int vrvq_rvq_expand_masked(const float* zst, int batch, int dim, int 
 
 extern "C" int vrvq_rvq_workspace(int batch, int frames, int nq, long long* bytes) {
   VRVQ_CHECK_ARG(bytes && batch > 0 && frames > 0 && nq > 0);
-  const long long nf = (long long)batch * frames;
-  // the fused path's partials are tagged granules (2 floats each)
-  *bytes = (long long)(2 * part_floats(nf, nq) + zst_floats(batch, frames, nq)) *
-               (long long)sizeof(float) + (long long)FU_SYNC_BYTES;
+  // An upper bound kept for the ABI (callers sized buffers with it): twice the partials, the
+  // larger of the zst rows and 8 KiB per clip and stage, and the sync block -- what the retired
+  // r04 launch took. vrvq_rvq_encode needs the partials once plus launch_pt's workspace
+  // (part_bytes + rvq_plan().ws_bytes, checked there), which is smaller at every shape: per clip
+  // and stage 256 T + max(32 T, 1024 ceil(T / F)) bytes with F >= min(T, 13).
+  const long long bnq = (long long)batch * nq;
+  *bytes = 2 * (long long)part_bytes((long long)batch * frames, nq) +
+           bnq * std::max(32LL * frames, 8192LL) + (long long)FU_SYNC_BYTES;
   return 0;
 }
 
@@ -2183,35 +1858,20 @@ extern "C" int vrvq_rvq_encode(const float* z, int batch, int dim, int frames, i
                  codes && latents && loss_pf && z_q && workspace);
   VRVQ_CHECK_ARG(batch > 0 && frames > 0 && nq > 0);
   if (!rvq_shape_ok(dim, cdim, nq, ncode)) return VRVQ_ERR_UNSUPPORTED;
-  long long need = 0;
-  vrvq_rvq_workspace(batch, frames, nq, &need);
-  VRVQ_CHECK_ARG(workspace_bytes >= need);
   VRVQ_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
-  const long long nf = (long long)batch * frames;
+  VRVQ_CHECK_ARG((long long)batch * frames * nq * RCD * PJ_SPLIT < 0x7fffffffLL);
+  // the partials, then launch_pt's workspace (vrvq_rvq_workspace() covers both at every shape)
+  const size_t part_b = part_bytes((long long)batch * frames, nq);
+  const long long pt_b = rvq_plan(batch, frames, nq, ncode, RESIDENT_UNUSED).ws_bytes;
+  VRVQ_CHECK_ARG(workspace_bytes >= (long long)part_b + pt_b);
   float* part = static_cast<float*>(workspace);
-  float* zst = part + part_floats(nf, nq);
   hipStream_t st = as_stream(stream);
-  if (g_rvq_path == 2 && frames <= PJ_TC && batch <= 0x7fffffff / (2 * FU_NP)) {
-    FusedArgs f{};
-    ChainArgs& c = f.c;
-    c.b_in = b_in; c.qb = qb; c.mcol = mcol; c.cb = cb; c.cbf = cbf; c.c2 = c2;
-    c.level = level;
-    f.w_in_t = w_in_t;
-    f.w_out = w_out;
-    f.b_out = b_out;
-    const int rc = launch_fused(f, RvqCall{batch, frames, nq, ncode, z, nullptr, imp, codes,
-                                          latents, loss_pf, z_q_is, z_q, mask, workspace,
-                                          (size_t)workspace_bytes, st});
-    if (rc != FUSED_NA) return rc;
-  }
-  int rc = launch_project(z, batch, frames, nq, w_in_t, part, st);
+  const int rc = launch_project(z, batch, frames, nq, w_in_t, part, st);
   if (rc) return rc;
-  rc = vrvq_rvq_chain(part, batch, frames, nq, ncode, cdim, b_in, qb, mcol, cb, cbf, c2, imp,
-                      level, codes, latents, loss_pf, zst, mask, stream);
-  if (rc) return rc;
-  return launch_expand(ExpandArgs{zst, batch, dim, frames, nq, w_out, b_out, imp, level, nullptr,
-                                  z_q_is, z_q, nullptr},
-                       st);
+  return launch_pt(rvq_weights(b_in, cb, cbf, c2, w_out, b_out, mcol, qb, level),
+                   RvqCall{batch, frames, nq, ncode, part, imp, codes, latents, loss_pf, z_q_is,
+                           z_q, mask, static_cast<char*>(workspace) + part_b,
+                           (size_t)workspace_bytes - part_b, st});
 }
 
 extern "C" int vrvq_rvq_w_in_planes_size(int nq, int dim, int cdim, long long* n_u16) {
@@ -2264,15 +1924,9 @@ extern "C" int vrvq_rvq_encode_part(const float* part, int batch, int dim, int f
   if (!rvq_shape_ok(dim, cdim, nq, ncode)) return VRVQ_ERR_UNSUPPORTED;
   VRVQ_CHECK_ARG((long long)batch * frames * nq * RCD * PJ_SPLIT < 0x7fffffffLL);
   VRVQ_CHECK_ARG(workspace_bytes >= rvq_plan(batch, frames, nq, ncode, RESIDENT_UNUSED).ws_bytes);
-  FusedArgs f{};
-  ChainArgs& c = f.c;
-  c.b_in = b_in; c.qb = qb; c.mcol = mcol; c.cb = cb; c.cbf = cbf; c.c2 = c2;
-  c.level = level;
-  f.w_out = w_out;
-  f.b_out = b_out;
-  return launch_pt(f, RvqCall{batch, frames, nq, ncode, nullptr, part, imp, codes, latents, loss_pf,
-                              z_q_is, z_q, mask, workspace, (size_t)workspace_bytes,
-                              as_stream(stream)});
+  return launch_pt(rvq_weights(b_in, cb, cbf, c2, w_out, b_out, mcol, qb, level),
+                   RvqCall{batch, frames, nq, ncode, part, imp, codes, latents, loss_pf, z_q_is,
+                           z_q, mask, workspace, (size_t)workspace_bytes, as_stream(stream)});
 }
 
 extern "C" int vrvq_rvq_fused_clips(int frames, int nq, int ncode, int* clips) {

@@ -355,18 +355,19 @@ Tensor rvq_frag(const Tensor& cbn) {
 }
 
 // A timeout of an earlier fused RVQ launch (include/vrvq.h vrvq_rvq_pending_error): its outputs
-// were poisoned (codes -1, NaN); raise here, at the next RVQ call, without synchronising.
+// were poisoned (NaN); raise here, at the next RVQ call, without synchronising.
 void check_pending_rvq_error() {
   int code = 0;
   check_rc(vrvq_rvq_pending_error(&code), "vrvq_rvq_pending_error");
   TORCH_CHECK(code == 0, "vrvq: an earlier fused RVQ launch timed out in an in-kernel hand-off "
-              "(code ", code, ": ", code == 1 ? "projection partials" : "stage rows",
-              "); its outputs are invalid (codes -1, NaN)");
+              "(code ", code, ": an expansion's wait for the chain's stage rows); its outputs are "
+              "invalid (NaN)");
 }
 
 // VBRResidualVectorQuantize.forward quantizer loop + gating (models/quantize.py:328-443) and
 // ResidualVectorQuantize.forward in eval (:136-214): all stages, z_q_is, mask, masked z_q.
-// The three launches' workspace comes from the caching allocator (stream-ordered reuse).
+// The workspace (partials, then the quantizer's) comes from the caching allocator
+// (stream-ordered reuse).
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rvq_encode(
     const Tensor& z, const Tensor& w_in_t, const Tensor& b_in, const Tensor& cb,
     const Tensor& cbf, const Tensor& c2, const Tensor& w_out, const Tensor& b_out,

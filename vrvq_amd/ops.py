@@ -209,8 +209,9 @@ def rvq_frag(cbn):
 def rvq_encode(z, w_in_t, b_in, cb, cbf, c2, w_out, b_out, mcol, qb, imp=None,
                level: float = 1.0, want_z_q_is: bool = True, want_mask: bool = True):
     """The residual quantizer over all nq = cb.shape[0] stages + importance gating
-    (VBRResidualVectorQuantize.forward, models/quantize.py:328-443): projection, 8-dim chain
-    and expansion (include/vrvq.h, vrvq_rvq_encode).
+    (VBRResidualVectorQuantize.forward, models/quantize.py:328-443) on channel-major z: the
+    projection launch, then the quantizer from its partials as rvq_encode_part runs it, at any T
+    (include/vrvq.h, vrvq_rvq_encode).
 
     Returns codes int64 [B,nq,T], latents [B,nq*d,T], loss_pf [B,nq,T], z_q_is [B,nq,D,T] (or
     None), z_q [B,D,T], mask [B,nq,T] (or None)."""
@@ -230,7 +231,7 @@ def rvq_encode_part(part, frames, b_in, cb, cbf, c2, w_out, b_out, mcol, qb, imp
                     level: float = 1.0, want_z_q_is: bool = True, want_mask: bool = True):
     """rvq_encode from conv1d_proj's partials (8, B*T, 8 nq): one launch per group of resident
     clips (include/vrvq.h vrvq_rvq_encode_part), or the chain + expansion launches where a clip
-    does not fit it. Same outputs as rvq_encode's three launches, bit for bit."""
+    does not fit it. Same outputs as rvq_encode (either launch structure), bit for bit."""
     codes, lat, loss, zqis, zq, mask = _ops().rvq_encode_part(part, int(frames), b_in, cb, cbf,
                                                             c2, w_out, b_out, mcol, qb, imp,
                                                             float(level), bool(want_z_q_is),

@@ -143,7 +143,7 @@ def masked_sum(z_q_is: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 def check_errors(device=None) -> None:
     """End-of-work check for the fused RVQ launches' bounded in-kernel waits (include/vrvq.h
     vrvq_rvq_pending_error): synchronises the device, then raises RuntimeError if any launch
-    completed by now timed out (its outputs were poisoned: codes -1, NaN z_q). The RVQ ops also
+    completed by now timed out (its outputs were poisoned: NaN z_q / z_q_is). The RVQ ops also
     raise on such a code at their next call; a one-shot caller (a single encode, the last call of
     a sweep) calls this after its own work instead. Clears the code it reports."""
     from . import _lib
@@ -151,9 +151,8 @@ def check_errors(device=None) -> None:
     code = _lib.rvq_pending_error()
     if code:
         raise RuntimeError(
-            f"vrvq: a fused RVQ launch timed out in an in-kernel hand-off (code {code}: "
-            f"{'projection partials' if code == 1 else 'stage rows'}); its outputs are invalid "
-            "(codes -1, NaN)")
+            f"vrvq: a fused RVQ launch timed out in an in-kernel hand-off (code {code}: an "
+            "expansion's wait for the chain's stage rows); its outputs are invalid (NaN)")
 
 
 def sweep_latents(imp_map: torch.Tensor, z_q_is: torch.Tensor, levels: Sequence[float],
