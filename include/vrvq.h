@@ -615,6 +615,51 @@ int vrvq_resample_adjoint(const float* dy, int rows, long long out_length, int o
                           int new_rate, int width, int ntaps, const float* taps, const int* first,
                           float* dx, long long length, vrvq_stream_t stream);
 
+/* Integrated loudness (library version 108): ITU-R BS.1770-4 as audiotools' AudioSignal.loudness /
+ * Meter.integrated_loudness computes it (models/dac_base.py:183 / :186 / :295 measure and
+ * normalize with it, conf/vrvq/vrvq_a2_lufs.yml VolumeNorm applies it to every batch), in the
+ * arithmetic of vrvq_amd.codec.loudness.
+ *
+ * x [items][channels][length] fp32 -> one fp64 LUFS per item, floored at -70. With sr = sample_rate:
+ *   K-weighting   two RBJ biquads in cascade, coefficients in fp64: high shelf +4 dB at 1500 Hz,
+ *                 Q = 1 / sqrt 2, then high pass at 38 Hz, Q = 0.5, each run in fp64 in the
+ *                 transposed direct form II (y = b0 x + s0; s0 = b1 x - a1 y + s1; s1 = b2 x - a2 y).
+ *   blocks        win = int(0.4 sr) samples every step = int(0.4 sr * 0.25); block j of a channel is
+ *                 the mean of y^2 over [j step, j step + win); blocks = (eff - win) / step + 1.
+ *   short input   length / sr < 0.5: eff = length + int((0.5 - length / sr) * sr), the samples past
+ *                 `length` read as zeros (the filter runs on through them); otherwise eff = length.
+ *   gating        l_j = -0.691 + 10 log10(sum_c G_c z_cj), G = 1, 1, 1, 1.41, 1.41; absolute gate
+ *                 l_j > -70; relative gate 10 LU under the loudness of the absolute-gated channel
+ *                 means; the result is the loudness of the means over the blocks past both gates,
+ *                 -70 where no block passes or the value is below -70.
+ * The recurrence is exact, not windowed: every lane owns VRVQ_LOUDNESS_CHUNK consecutive samples of
+ * one (item, channel) row. Pass 1 runs the cascade over each chunk from zero state and stores the
+ * four final state values; a carry launch (one wave per row, fixed order) turns them into each
+ * chunk's entry state with the chunk transition s' = M1 s, t' = M2 t + K s (the 4 x 4 power of the
+ * zero-input cascade, built on the host in long double and rounded once); pass 2 reruns every
+ * chunk from its entry state and adds y^2 in fp64 into partial sums cut at the chunk edges and at
+ * the block edges; a finish launch (one workgroup per item) adds them into blocks and evaluates the
+ * gates. The filtered signal is never stored. No atomics, no host sync; every sum has a fixed
+ * order that depends on (sample_rate, channels, length) alone, so an item's bits do not depend on
+ * the other items or their number.
+ * Supported: sample_rate >= 10 (step >= 1), 1 <= channels <= 5, 1 <= length <= 2^40,
+ * items * channels <= 65535. Anything else: VRVQ_ERR_ARG, and vrvq_loudness_error() names it.
+ *
+ *   vrvq_loudness_plan   host only, touches no device. out[VRVQ_LOUDNESS_PLAN_LEN] doubles (the
+ *                        integers exactly): {eff, win, step, blocks, chunk, chunks per row,
+ *                        workspace bytes per item, partial sums per row,
+ *                        shelf b0 b1 b2 a1 a2, high pass b0 b1 b2 a1 a2 (a0 = 1),
+ *                        M1[2][2], M2[2][2], K[2][2] row-major}.
+ *   vrvq_loudness        out_lufs [items] fp64 from x, both in device memory. workspace: items times
+ *                        the plan's bytes, 8-byte aligned, device memory; its contents on entry do
+ *                        not matter. */
+#define VRVQ_LOUDNESS_CHUNK 256
+#define VRVQ_LOUDNESS_PLAN_LEN 30
+int vrvq_loudness_plan(int sample_rate, int channels, long long length, double* out);
+const char* vrvq_loudness_error(void);
+int vrvq_loudness(const float* x, int items, int channels, long long length, int sample_rate,
+                  void* workspace, double* out_lufs, vrvq_stream_t stream);
+
 /* Variable-length code packing from importance masks (the reference's
  * DACFile, models/dac_base.py:19-58, stores the full uint16 code matrix). Packed stream is
  * clip-major, frame-major, stage-minor uint16: packed[clip_off[b] + frame_off[b,t] + i] =

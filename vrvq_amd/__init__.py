@@ -13,6 +13,7 @@ from .utils import (cal_bpf_from_mask, cal_bpf_tensor, check_errors, generate_ma
                     mel_distance, rd_sweep, scale_importance, signal_metrics, solve_levels,
                     solve_quality, spectral_distance, stft_distance)
 from .resampling import resample
+from .metering import loudness, normalize_loudness
 from .config import from_config, load_config, model_kwargs
 
 __all__ = [
@@ -23,5 +24,5 @@ __all__ = [
     "masked_sum", "scale_importance", "level_sweep", "load_config", "model_kwargs",
     "from_config", "check_errors", "rate_curve", "solve_levels", "kbps_to_budget",
     "signal_metrics", "rd_sweep", "solve_quality", "spectral_distance", "mel_distance",
-    "stft_distance", "resample",
+    "stft_distance", "resample", "loudness", "normalize_loudness",
 ]

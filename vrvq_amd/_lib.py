@@ -78,6 +78,8 @@ SIGNATURES = {
                       _P],
     "vrvq_resample_adjoint": [_P, _I, ctypes.c_longlong, _I, _I, _I, _I, _P, _P, _P,
                               ctypes.c_longlong, _P],
+    "vrvq_loudness_plan": [_I, _I, ctypes.c_longlong, _P],
+    "vrvq_loudness": [_P, _I, _I, ctypes.c_longlong, _I, _P, _P, _P],
     "vrvq_pack_counts": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "vrvq_pack_codes": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "vrvq_unpack_offsets": [_P, _I, _I, _P, _P, _P],
@@ -108,11 +110,14 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_debug": ([ctypes.c_uint, ctypes.c_uint], _I),
          "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I),
          "vrvq_conv_plan": ([_I] * 11 + [_P], _I),
-         "vrvq_resample_error": ([], ctypes.c_char_p)}
+         "vrvq_resample_error": ([], ctypes.c_char_p),
+         "vrvq_loudness_error": ([], ctypes.c_char_p)}
 
 METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
 SPECTRAL_TILE_SAMPLES = 8192  # VRVQ_SPECTRAL_TILE_SAMPLES (tests/test_spectral.py compares)
 RESAMPLE_TILE = 512  # VRVQ_RESAMPLE_TILE (tests/test_resample.py compares)
+LOUDNESS_CHUNK = 256  # VRVQ_LOUDNESS_CHUNK (tests/test_loudness.py compares)
+LOUDNESS_PLAN_LEN = 30  # VRVQ_LOUDNESS_PLAN_LEN
 
 
 def spectral_tile_frames(window: int) -> int:
@@ -291,3 +296,32 @@ def resample_taps(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.
                    taps.ctypes.data_as(ctypes.c_void_p), taps.size,
                    first.ctypes.data_as(ctypes.c_void_p), first.size)
     return taps, first
+
+
+LOUDNESS_PLAN_INTS = ("eff_length", "win", "step", "blocks", "chunk", "chunks", "ws_bytes",
+                      "pieces")
+
+
+def loudness_plan(sample_rate: int, channels: int, length: int) -> dict:
+    """How vrvq_loudness measures `length` samples of `channels` channels at `sample_rate`
+    (include/vrvq.h vrvq_loudness_plan; no GPU needed): the integers LOUDNESS_PLAN_INTS (eff_length
+    counts the zeros a signal under 0.5 s is measured with, ws_bytes is per item), "shelf" and
+    "highpass" = (b0, b1, b2, a1, a2) with a0 = 1, and the chunk transition "M1", "M2", "K" as
+    2 x 2 NumPy float64 arrays (s' = M1 s, t' = M2 t + K s over one chunk of zero input). Raises
+    RuntimeError with the library's reason where the arguments are unsupported."""
+    import numpy as np
+
+    out = (ctypes.c_double * LOUDNESS_PLAN_LEN)()
+    lib = load()
+    rc = lib.vrvq_loudness_plan(int(sample_rate), int(channels), int(length), out)
+    if rc != 0:
+        why = lib.vrvq_loudness_error() or lib.vrvq_status_string(rc)
+        raise RuntimeError(f"vrvq_loudness_plan failed ({rc}): "
+                           f"{why.decode() if why else 'unknown'}")
+    v = [float(d) for d in out]
+    plan = {k: int(v[i]) for i, k in enumerate(LOUDNESS_PLAN_INTS)}
+    plan["shelf"] = tuple(v[8:13])
+    plan["highpass"] = tuple(v[13:18])
+    for i, k in enumerate(("M1", "M2", "K")):
+        plan[k] = np.array(v[18 + 4 * i:22 + 4 * i]).reshape(2, 2)
+    return plan

@@ -10,10 +10,13 @@ What the reference body does, and how it runs here:
 * loudness (`AudioSignal.loudness`, descript-audiotools >= 0.7.2, absent from this image): the
   ITU-R BS.1770-4 integrated loudness of audiotools' `Meter` — K-weighting (high shelf
   +4 dB @ 1500 Hz, Q 1/sqrt2; high pass 38 Hz, Q 0.5; RBJ biquads), 400 ms blocks with 75 %
-  overlap, absolute gate -70 LUFS, relative gate -10 LU, floor -70 — restated in `loudness`
-  (float64 IIR on the host: one scalar per signal, audiotools' own CPU path uses
-  scipy.signal.lfilter the same way). Input shorter than 0.5 s is zero-padded to 0.5 s for the
-  measurement, as audiotools does.
+  overlap, absolute gate -70 LUFS, relative gate -10 LU, floor -70. Input shorter than 0.5 s is
+  zero-padded to 0.5 s for the measurement, as audiotools does. `compress` and `decompress`
+  measure on the device (vrvq_amd.loudness: the HIP chunked scan of include/vrvq.h "Integrated
+  loudness", the exact fp64 recurrence, no copy of the signal to the host and no sync): compress
+  measures once, reuses the value for the normalisation and moves it to the host with the codes.
+  `loudness` below is the host restatement (float64 scipy.signal.lfilter, as audiotools' own CPU
+  path) that CPU tensors take and the device path is tested against.
 * `normalize(normalize_db)` and `ensure_max_of_audio()` (peak <= 1 per channel) — elementwise
   gains on the device.
 * resampling (`AudioSignal.resample`, julius.resample_frac): a file at another rate is converted
@@ -174,7 +177,11 @@ def loudness(audio_data: torch.Tensor, sample_rate: int, block_size: float = 0.4
 
 
 def normalize(audio_data: torch.Tensor, sample_rate: int, db) -> torch.Tensor:
-    """AudioSignal.normalize: gain = exp((db - loudness) * ln10 / 20) per item."""
+    """AudioSignal.normalize: gain = exp((db - loudness) * ln10 / 20) per item. Audio on a GPU
+    is measured there (vrvq_amd.normalize_loudness, no host sync); anything else on the host."""
+    if audio_data.is_cuda:
+        from .metering import normalize_loudness
+        return normalize_loudness(audio_data, sample_rate, db)
     ref = loudness(audio_data, sample_rate).to(audio_data.device)
     db = torch.as_tensor(db, dtype=torch.float32).to(audio_data.device)
     gain = torch.exp((db - ref) * GAIN_FACTOR)
@@ -247,9 +254,11 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
         # rate, the loudness included (models/dac_base.py:181-183)
         from .resampling import resample
         audio = resample(audio, original_sr, model.sample_rate)
-    input_db = loudness(audio, model.sample_rate)
+    # measured once, on the audio's device; it stays there until the DACFile is built
+    from .metering import loudness as measure, loudness_gain
+    input_db = measure(audio, model.sample_rate)
     if normalize_db is not None:
-        audio = normalize(audio, model.sample_rate, normalize_db)
+        audio = audio * loudness_gain(input_db, normalize_db).reshape(-1, 1, 1)
     audio = ensure_max_of_audio(audio)
 
     nb, nac, nt = audio.shape
@@ -316,7 +325,7 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
         codes = codes.reshape(nw, nb * nac, codes.shape[1], chunk_length)
         codes = codes.permute(1, 2, 0, 3).reshape(nb * nac, -1, nw * chunk_length)
         dac = DACFile(codes=codes.cpu(), chunk_length=chunk_length,
-                      original_length=original_length, input_db=input_db, channels=nac,
+                      original_length=original_length, input_db=input_db.cpu(), channels=nac,
                       sample_rate=original_sr, padding=model.padding,
                       dac_version=SUPPORTED_VERSIONS[-1])
     finally:

@@ -1291,6 +1291,31 @@ Tensor resample_adjoint(const Tensor& dy, const Tensor& taps, const Tensor& firs
   return dx;
 }
 
+// ----------------------------------------------------------------------------- loudness
+// audiotools' AudioSignal.loudness (Meter.integrated_loudness, BS.1770-4), include/vrvq.h
+// "Integrated loudness": x (items, channels, samples) -> float64 LUFS (items,), floored at -70.
+Tensor loudness(const Tensor& x, int64_t sample_rate) {
+  check_t(x, "x");
+  TORCH_CHECK_VALUE(x.dim() == 3 && x.numel() > 0,
+                    "loudness: x must be (items, channels, samples), none of them empty");
+  TORCH_CHECK_VALUE(sample_rate > 0 && sample_rate < (1LL << 31),
+                    "loudness: the sample rate must be positive (got ", sample_rate, ")");
+  c10::DeviceGuard guard(x.device());
+  const int64_t items = x.size(0), nch = x.size(1), L = x.size(2);
+  TORCH_CHECK_VALUE(nch <= 5, "loudness: 1 to 5 channels have a BS.1770 gain (got ", nch, ")");
+  TORCH_CHECK_VALUE(items * nch <= 65535, "loudness: at most 65535 (item, channel) rows");
+  double plan[VRVQ_LOUDNESS_PLAN_LEN];
+  const int prc = vrvq_loudness_plan((int)sample_rate, (int)nch, L, plan);
+  TORCH_CHECK_VALUE(prc == 0, "vrvq_loudness_plan failed (", prc, "): ", vrvq_loudness_error());
+  const int64_t ws_doubles = items * ((int64_t)plan[6] / 8);
+  Tensor ws = at::empty({ws_doubles}, x.options().dtype(at::kDouble));
+  Tensor out = at::empty({items}, x.options().dtype(at::kDouble));
+  check_rc(vrvq_loudness(x.data_ptr<float>(), (int)items, (int)nch, L, (int)sample_rate,
+                         ws.data_ptr<double>(), out.data_ptr<double>(), stream_of(x)),
+           "vrvq_loudness");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vrvq, m) {
@@ -1389,6 +1414,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.def(
       "resample_adjoint(Tensor dy, Tensor taps, Tensor first, int old_rate, int width, "
       "int length) -> Tensor");
+  m.def("loudness(Tensor x, int sample_rate) -> Tensor");
 }
 
 #define VRVQ_IMPLS(m) \
@@ -1437,6 +1463,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("rvq_backward", &rvq_backward); \
   m.impl("resample", &resample); \
   m.impl("resample_adjoint", &resample_adjoint); \
+  m.impl("loudness", &loudness); \
 
 TORCH_LIBRARY_IMPL(vrvq, CUDA, m) { VRVQ_IMPLS(m) }
 

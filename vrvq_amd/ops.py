@@ -350,6 +350,13 @@ def resample_adjoint(dy: torch.Tensor, taps: torch.Tensor, first: torch.Tensor, 
     return _ops().resample_adjoint(dy, taps, first, int(old_rate), int(width), int(length))
 
 
+def loudness(x: torch.Tensor, sample_rate: int) -> torch.Tensor:
+    """BS.1770-4 integrated loudness of x (items, channels <= 5, samples) float32: float64 LUFS
+    (items,), floored at -70, in four launches and without a host sync (include/vrvq.h
+    "Integrated loudness"; vrvq_amd.loudness is the front end)."""
+    return _ops().loudness(x, int(sample_rate))
+
+
 # ----------------------------------------------------------------------------- training step
 # Backward operators of the generator (include/vrvq.h "Training step"; vrvq_amd/train.py).
 def conv1d_wgrad(a, x, k: int, stride: int = 1, pad: int = 0, dil: int = 1,
@@ -584,6 +591,10 @@ def _register_fakes():
     @reg("vrvq::resample_adjoint")
     def _(dy, taps, first, old_rate, width, length):
         return f32(dy, (dy.shape[0], length))
+
+    @reg("vrvq::loudness")
+    def _(x, sample_rate):
+        return x.new_empty((x.shape[0],), dtype=torch.float64)
 
     @reg("vrvq::pack_counts")
     def _(mask):
