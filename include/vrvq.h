@@ -564,6 +564,52 @@ int vrvq_spectral_distance(const float* est, const float* ref, int rows, int ref
                            double* terms, double* distance, void* workspace,
                            long long workspace_bytes, vrvq_stream_t stream);
 
+/* Gradient of the spectral distance (library version 109): grad_est [rows][samples] fp32 =
+ * grad_distance[row] * d distance[row] / d est[row], grad_distance [rows] fp64 on the device; the
+ * reference gets no gradient. Arguments, tables and argument rules are vrvq_spectral_distance's.
+ * With the definitions above, for one row and one scale, N = elements * frames:
+ *   g[m,j] = (log_weight pow / (ln 10 E) sgn(pow log10 max(E, eps) - pow log10 max(R, eps)) [E >= eps]
+ *             + mag_weight sgn(E - R)) / N, sgn(0) = 0, formed in fp64 with grad_distance[row]
+ *   and rounded once (the clamp passes the gradient where E >= eps, as torch.clamp's backward);
+ *   to the bins G[k] = sum_m weights[m,k] g[m,j] in ascending m (fp32 fma chain; G[k] = g[k,j]
+ *   for n_mels == 0); through the magnitude G[k] X[k] / |X[k]|, 0 where |X[k]| = 0; through the
+ *   adjoint of the one-sided real transform (bins 0 .. W/2 each once), times the window;
+ *   overlap-add of the frames at hop W/4; the adjoint of the reflection (what landed at padded
+ *   position -i is added to sample i, at n-1+i to n-1-i); the scales added in their order.
+ * E, R and X are recomputed by the forward's own code (its bits); nothing of the forward is saved.
+ * A bin whose fp32 magnitude is under 2^-6 of its frame's rms magnitude is ill-conditioned (an
+ * ulp of the rms is 2^-18 of it or more, and X / |X| and 1 / E carry that on). How many bins
+ * that is depends on the spectrum's flatness: a handful per tile for a flat spectrum, most bins
+ * for a steep one. Where a batch of frames (2048 / W of them) has at most 32 such bins, each X[k]
+ * is summed again from the samples in fp64 (one wave per bin, window and twiddle in fp64, a fixed
+ * tree) and that X / |X|, and for n_mels == 0 that |X| in 1 / E, are used; the sign and clamp
+ * decisions stay those of the fp32 E and R. A batch with more keeps the fp32 values for all of
+ * them, so the pass costs at most 32 bins (eight rounds of the workgroup's four waves) per batch.
+ * est == ref bitwise and an all-zero est give exactly 0; samples past a row's length get 0; a row
+ * with n <= W/2 at some scale gets NaN in all `samples` entries; NaN in a row's data gives NaN at
+ * the samples of the frames that hold it and leaves every other row untouched.
+ *
+ * n_scales + 1 launches on `stream`, no float atomics. A workgroup owns the forward's tile of
+ * VRVQ_SPECTRAL_TILE_FRAMES(W) frames, overlap-adds them in ascending frame order (fp32 fma chain
+ * from 0) into its span of SPAN(W) = W + (frames per tile - 1) W/4 samples and stores the span to
+ * workspace; adjacent spans overlap by 3 W/4 samples. The last launch computes each sample as:
+ * per scale, tile t's entry then tile t+1's for the sample itself, then the same for the left
+ * fold, then for the right fold; then the scales in their order, all fp32 adds in that order.
+ * The order is a function of (scale, frame, sample) alone: a row's bits do not depend on the other
+ * rows, on their number, on the row's address or on whether lengths or `samples` gave its length.
+ * VRVQ_ERR_ARG as for vrvq_spectral_distance, and for a null grad_distance or grad_est.
+ *   vrvq_spectral_distance_grad_workspace  *bytes = 4 * rows * sum_s tiles_s * SPAN(W_s) rounded
+ *                                          up to 8, tiles_s as in the forward's formula */
+int vrvq_spectral_distance_grad_workspace(int rows, long long samples, int n_scales,
+                                          const int* windows, long long* bytes);
+int vrvq_spectral_distance_grad(const float* est, const float* ref, int rows, int ref_rows,
+                                long long samples, const long long* lengths, int n_scales,
+                                const int* windows, const int* n_mels, const float* const* tables,
+                                const int* const* bands, const float* const* band_weights,
+                                double clamp_eps, double pow, double log_weight, double mag_weight,
+                                const double* grad_distance, float* grad_est, void* workspace,
+                                long long workspace_bytes, vrvq_stream_t stream);
+
 /* Sample-rate conversion (library version 106): julius.resample_frac as
  * audiotools.AudioSignal.resample calls it (zeros = 24, rolloff = 0.945), which the reference runs
  * in scripts/inference.py:187, models/dac_base.py:182 / :296 and models/discriminator.py:87. A

@@ -71,6 +71,10 @@ SIGNATURES = {
     "vrvq_spectral_distance": [_P, _P, _I, _I, ctypes.c_longlong, _P, _I, _P, _P, _P, _P, _P,
                                ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                _P, _P, _P, ctypes.c_longlong, _P],
+    "vrvq_spectral_distance_grad_workspace": [_I, ctypes.c_longlong, _I, _P, _P],
+    "vrvq_spectral_distance_grad": [_P, _P, _I, _I, ctypes.c_longlong, _P, _I, _P, _P, _P, _P, _P,
+                                    ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, _P, _P, _P, ctypes.c_longlong, _P],
     "vrvq_resample_plan": [_I, _I, _I, ctypes.c_double, ctypes.c_longlong, _P],
     "vrvq_resample_taps": [_I, _I, _I, ctypes.c_double, _P, ctypes.c_longlong, _P,
                            ctypes.c_longlong],

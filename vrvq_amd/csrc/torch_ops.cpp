@@ -788,17 +788,28 @@ std::tuple<Tensor, Tensor> signal_metrics(const Tensor& est, const Tensor& ref,
 // per row and scale (include/vrvq.h "Spectral distance"). est (R, T) or (R, 1, T), ref (B, T) or
 // (B, 1, T), lengths (B,) int64 or None; per scale tables (3 W,) float32, bands (3, n_mels) int32
 // and weights float32 (both empty for n_mels == 0) -> terms (R, S, 2) and distance (R,), fp64.
-std::tuple<Tensor, Tensor> spectral_distance(const Tensor& est, const Tensor& ref, const optional<Tensor>& lengths,
-                         at::IntArrayRef windows, at::IntArrayRef n_mels, at::TensorList tables,
-                         at::TensorList bands, at::TensorList weights, double clamp_eps,
-                         double pow, double log_weight, double mag_weight) {
+struct SpectralArgs {  // the checked, marshalled arguments both spectral operators share
+  int64_t R, B, T;
+  std::vector<int> win, nm;
+  std::vector<const float*> tab, wts;
+  std::vector<const int*> bnd;
+  const long long* lengths;
+};
+
+SpectralArgs spectral_args(const Tensor& est, const Tensor& ref, const optional<Tensor>& lengths,
+                           at::IntArrayRef windows, at::IntArrayRef n_mels, at::TensorList tables,
+                           at::TensorList bands, at::TensorList weights) {
+  SpectralArgs a;
   check_t(est, "est");
   check_on(ref, est, "ref");
   TORCH_CHECK(est.dim() >= 2 && est.numel() > 0 && est.numel() == est.size(0) * est.size(-1),
               "spectral_distance: est must be (R, T) or (R, 1, T)");
   TORCH_CHECK(ref.dim() >= 2 && ref.numel() > 0 && ref.numel() == ref.size(0) * ref.size(-1),
               "spectral_distance: ref must be (B, T) or (B, 1, T)");
-  const int64_t R = est.size(0), B = ref.size(0), T = est.size(-1);
+  a.R = est.size(0);
+  a.B = ref.size(0);
+  a.T = est.size(-1);
+  const int64_t R = a.R, B = a.B, T = a.T;
   TORCH_CHECK(ref.size(-1) == T, "spectral_distance: est has ", T, " samples, ref ",
               ref.size(-1));
   TORCH_CHECK(R % B == 0, "spectral_distance: ", R, " rows are no multiple of ", B,
@@ -813,9 +824,11 @@ std::tuple<Tensor, Tensor> spectral_distance(const Tensor& est, const Tensor& re
   TORCH_CHECK(S >= 1 && S <= 16 && n_mels.size() == S && tables.size() == S && bands.size() == S &&
                   weights.size() == S,
               "spectral_distance: 1 to 16 scales, one n_mels, tables, bands and weights each");
-  std::vector<int> win(S), nm(S);
-  std::vector<const float*> tab(S), wts(S);
-  std::vector<const int*> bnd(S);
+  a.win.resize(S);
+  a.nm.resize(S);
+  a.tab.resize(S);
+  a.wts.resize(S);
+  a.bnd.resize(S);
   for (size_t s = 0; s < S; ++s) {
     const int64_t W = windows[s], M = n_mels[s];
     TORCH_CHECK(W >= 32 && W <= 2048 && (W & (W - 1)) == 0, "spectral_distance: window ", W,
@@ -829,28 +842,66 @@ std::tuple<Tensor, Tensor> spectral_distance(const Tensor& est, const Tensor& re
       TORCH_CHECK(bands[s].numel() == 3 * M, "spectral_distance: bands[", s, "] must be (3, ", M,
                   ")");
     }
-    win[s] = (int)W;
-    nm[s] = (int)M;
-    tab[s] = tables[s].data_ptr<float>();
-    bnd[s] = M > 0 ? bands[s].data_ptr<int>() : nullptr;
-    wts[s] = M > 0 ? weights[s].data_ptr<float>() : nullptr;
+    a.win[s] = (int)W;
+    a.nm[s] = (int)M;
+    a.tab[s] = tables[s].data_ptr<float>();
+    a.bnd[s] = M > 0 ? bands[s].data_ptr<int>() : nullptr;
+    a.wts[s] = M > 0 ? weights[s].data_ptr<float>() : nullptr;
   }
+  a.lengths = lengths.has_value()
+                  ? reinterpret_cast<const long long*>(lengths->data_ptr<int64_t>())
+                  : nullptr;
+  return a;
+}
+
+std::tuple<Tensor, Tensor> spectral_distance(const Tensor& est, const Tensor& ref, const optional<Tensor>& lengths,
+                         at::IntArrayRef windows, at::IntArrayRef n_mels, at::TensorList tables,
+                         at::TensorList bands, at::TensorList weights, double clamp_eps,
+                         double pow, double log_weight, double mag_weight) {
+  const SpectralArgs a = spectral_args(est, ref, lengths, windows, n_mels, tables, bands, weights);
+  const int S = (int)a.win.size();
   c10::DeviceGuard guard(est.device());
   long long ws_bytes = 0;
-  check_rc(vrvq_spectral_distance_workspace((int)R, T, (int)S, win.data(), &ws_bytes),
+  check_rc(vrvq_spectral_distance_workspace((int)a.R, a.T, S, a.win.data(), &ws_bytes),
            "vrvq_spectral_distance_workspace");
-  Tensor terms = at::empty({R, (int64_t)S, 2}, est.options().dtype(at::kDouble));
-  Tensor distance = at::empty({R}, est.options().dtype(at::kDouble));
+  Tensor terms = at::empty({a.R, (int64_t)S, 2}, est.options().dtype(at::kDouble));
+  Tensor distance = at::empty({a.R}, est.options().dtype(at::kDouble));
   Tensor ws = at::empty({ws_bytes / 8}, est.options().dtype(at::kDouble));
   check_rc(vrvq_spectral_distance(
-               est.data_ptr<float>(), ref.data_ptr<float>(), (int)R, (int)B, T,
-               lengths.has_value() ? reinterpret_cast<const long long*>(lengths->data_ptr<int64_t>())
-                                   : nullptr,
-               (int)S, win.data(), nm.data(), tab.data(), bnd.data(), wts.data(), clamp_eps, pow,
+               est.data_ptr<float>(), ref.data_ptr<float>(), (int)a.R, (int)a.B, a.T, a.lengths, S,
+               a.win.data(), a.nm.data(), a.tab.data(), a.bnd.data(), a.wts.data(), clamp_eps, pow,
                log_weight, mag_weight, terms.data_ptr<double>(), distance.data_ptr<double>(),
                ws.data_ptr<double>(), ws_bytes, stream_of(est)),
            "vrvq_spectral_distance");
   return {terms, distance};
+}
+
+// The gradient of spectral_distance's distance with respect to est, scaled per row by
+// grad_distance (R,) fp64: (R, T) float32 (include/vrvq.h vrvq_spectral_distance_grad). Same
+// arguments and checks; ref gets no gradient.
+Tensor spectral_distance_grad(const Tensor& est, const Tensor& ref,
+                              const optional<Tensor>& lengths, at::IntArrayRef windows,
+                              at::IntArrayRef n_mels, at::TensorList tables, at::TensorList bands,
+                              at::TensorList weights, double clamp_eps, double pow,
+                              double log_weight, double mag_weight, const Tensor& grad_distance) {
+  const SpectralArgs a = spectral_args(est, ref, lengths, windows, n_mels, tables, bands, weights);
+  const int S = (int)a.win.size();
+  check_on(grad_distance, est, "grad_distance", at::kDouble);
+  TORCH_CHECK(grad_distance.dim() == 1 && grad_distance.numel() == a.R,
+              "spectral_distance_grad: one grad_distance per row of est");
+  c10::DeviceGuard guard(est.device());
+  long long ws_bytes = 0;
+  check_rc(vrvq_spectral_distance_grad_workspace((int)a.R, a.T, S, a.win.data(), &ws_bytes),
+           "vrvq_spectral_distance_grad_workspace");
+  Tensor grad = at::empty({a.R, a.T}, est.options());
+  Tensor ws = at::empty({ws_bytes / 8}, est.options().dtype(at::kDouble));
+  check_rc(vrvq_spectral_distance_grad(
+               est.data_ptr<float>(), ref.data_ptr<float>(), (int)a.R, (int)a.B, a.T, a.lengths, S,
+               a.win.data(), a.nm.data(), a.tab.data(), a.bnd.data(), a.wts.data(), clamp_eps, pow,
+               log_weight, mag_weight, grad_distance.data_ptr<double>(), grad.data_ptr<float>(),
+               ws.data_ptr<double>(), ws_bytes, stream_of(est)),
+           "vrvq_spectral_distance_grad");
+  return grad;
 }
 
 // --------------------------------------------------------------------------- code packing
@@ -1376,6 +1427,10 @@ TORCH_LIBRARY(vrvq, m) {
       "spectral_distance(Tensor est, Tensor ref, Tensor? lengths, int[] windows, int[] n_mels, "
       "Tensor[] tables, Tensor[] bands, Tensor[] weights, float clamp_eps, float pow, "
       "float log_weight, float mag_weight) -> (Tensor terms, Tensor distance)");
+  m.def(
+      "spectral_distance_grad(Tensor est, Tensor ref, Tensor? lengths, int[] windows, "
+      "int[] n_mels, Tensor[] tables, Tensor[] bands, Tensor[] weights, float clamp_eps, "
+      "float pow, float log_weight, float mag_weight, Tensor grad_distance) -> Tensor");
   m.def("pack_counts(Tensor mask) -> (Tensor, Tensor, Tensor)");
   m.def(
       "pack_codes(Tensor codes, Tensor counts, Tensor clip_off, int total, int ncode) "
@@ -1447,6 +1502,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("scale_imp_rows", &scale_imp_rows); \
   m.impl("signal_metrics", &signal_metrics); \
   m.impl("spectral_distance", &spectral_distance); \
+  m.impl("spectral_distance_grad", &spectral_distance_grad); \
   m.impl("pack_counts", &pack_counts); \
   m.impl("pack_codes", &pack_codes); \
   m.impl("unpack_offsets", &unpack_offsets); \

@@ -63,6 +63,27 @@ def mel_spectrogram(x, sr: int, n_mels: int, window_length: int, hop_length: int
 
 
 # ------------------------------------------------------------------ losses
+def _fused_check(x, y, windows, name: str) -> None:
+    """The argument errors of a fused=True loss, raised before any launch."""
+    for w in windows:
+        if not (32 <= int(w) <= 2048 and int(w) & (int(w) - 1) == 0):
+            raise ValueError(f"{name}(fused=True): window {w} is no power of two in [32, 2048]")
+    for t, what in ((x, "x"), (y, "y")):
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[1] != 1:
+            raise ValueError(f"{name}(fused=True): {what} must be (B, 1, T)")
+    if x.shape != y.shape:
+        raise ValueError(f"{name}(fused=True): x {tuple(x.shape)} against y {tuple(y.shape)}")
+    if y.requires_grad:
+        raise ValueError(f"{name}(fused=True): y gets no gradient and must not require one")
+
+
+def _fused_loss(x, y, **kw):
+    """The batch mean of utils.spectral_distance's per-clip distance (fp64) in x's dtype: the
+    HIP forward and, where x requires a gradient, the HIP backward."""
+    from .utils import spectral_distance
+    return spectral_distance(x, y, **kw)["distance"].mean().to(x.dtype)
+
+
 class L1Loss(nn.Module):
     """models/loss.py:19-56 on waveforms."""
 
@@ -76,17 +97,24 @@ class L1Loss(nn.Module):
 
 class MultiScaleSTFTLoss(nn.Module):
     """models/loss.py:168-254: L1 of log10(|X|^pow clamped) (+ mag_weight * L1 of |X|) per
-    window length (hop = window / 4)."""
+    window length (hop = window / 4). fused=True computes the same loss and its gradient to x
+    in the HIP kernels of utils.spectral_distance (windows powers of two in [32, 2048], (B, 1, T)
+    inputs, no gradient to y: ValueError otherwise); the default is the torch composition."""
 
     def __init__(self, window_lengths: Sequence[int] = (2048, 512), clamp_eps: float = 1e-5,
                  mag_weight: float = 1.0, log_weight: float = 1.0, pow: float = 2.0,
-                 weight: float = 1.0):
+                 weight: float = 1.0, fused: bool = False):
         super().__init__()
         self.window_lengths = list(window_lengths)
         self.clamp_eps, self.mag_weight, self.log_weight = clamp_eps, mag_weight, log_weight
-        self.pow, self.weight = pow, weight
+        self.pow, self.weight, self.fused = pow, weight, bool(fused)
 
     def forward(self, x, y):
+        if self.fused:
+            _fused_check(x, y, self.window_lengths, "MultiScaleSTFTLoss")
+            return _fused_loss(x, y, windows=self.window_lengths, n_mels=None,
+                               clamp_eps=self.clamp_eps, pow=self.pow,
+                               log_weight=self.log_weight, mag_weight=self.mag_weight)
         loss = 0.0
         for w in self.window_lengths:
             xm = stft(x, w, w // 4).abs()
@@ -100,13 +128,15 @@ class MultiScaleSTFTLoss(nn.Module):
 
 class MelSpectrogramLoss(nn.Module):
     """models/loss.py:257-401 (levels=None branch); defaults are conf/base.yml's
-    (7 scales, n_mels 5..320, windows 32..2048, pow 1, mag_weight 0)."""
+    (7 scales, n_mels 5..320, windows 32..2048, pow 1, mag_weight 0). fused=True as in
+    MultiScaleSTFTLoss, with the module's own scales, n_mels, fmin / fmax, eps, pow and weights."""
 
     def __init__(self, n_mels: Sequence[int] = (5, 10, 20, 40, 80, 160, 320),
                  window_lengths: Sequence[int] = (32, 64, 128, 256, 512, 1024, 2048),
                  clamp_eps: float = 1e-5, mag_weight: float = 0.0, log_weight: float = 1.0,
                  pow: float = 1.0, weight: float = 1.0, mel_fmin: Sequence[float] = None,
-                 mel_fmax: Sequence[Optional[float]] = None, sample_rate: int = 44100):
+                 mel_fmax: Sequence[Optional[float]] = None, sample_rate: int = 44100,
+                 fused: bool = False):
         super().__init__()
         self.n_mels = list(n_mels)
         self.window_lengths = list(window_lengths)
@@ -114,8 +144,16 @@ class MelSpectrogramLoss(nn.Module):
         self.mel_fmax = list(mel_fmax) if mel_fmax is not None else [None] * len(self.n_mels)
         self.clamp_eps, self.mag_weight, self.log_weight = clamp_eps, mag_weight, log_weight
         self.pow, self.weight, self.sample_rate = pow, weight, sample_rate
+        self.fused = bool(fused)
 
     def forward(self, x, y):
+        if self.fused:
+            _fused_check(x, y, self.window_lengths, "MelSpectrogramLoss")
+            return _fused_loss(x, y, windows=self.window_lengths, n_mels=self.n_mels,
+                               clamp_eps=self.clamp_eps, pow=self.pow,
+                               log_weight=self.log_weight, mag_weight=self.mag_weight,
+                               mel_fmin=self.mel_fmin, mel_fmax=self.mel_fmax,
+                               sample_rate=self.sample_rate)
         loss = 0.0
         for n, w, lo, hi in zip(self.n_mels, self.window_lengths, self.mel_fmin, self.mel_fmax):
             xm = mel_spectrogram(x, self.sample_rate, n, w, w // 4, lo, hi)

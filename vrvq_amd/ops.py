@@ -336,6 +336,20 @@ def spectral_distance(est: torch.Tensor, ref: torch.Tensor, lengths: Optional[to
                                     float(log_weight), float(mag_weight))
 
 
+def spectral_distance_grad(est: torch.Tensor, ref: torch.Tensor, lengths: Optional[torch.Tensor],
+                           windows, n_mels, tables, bands, weights, clamp_eps: float, pow: float,
+                           log_weight: float, mag_weight: float,
+                           grad_distance: torch.Tensor) -> torch.Tensor:
+    """grad_distance[r] * d distance[r] / d est[r] of spectral_distance with the same arguments,
+    float32 (R, T), in S + 1 launches and without a host sync; grad_distance is float64 (R,). The
+    spectra are recomputed, nothing of the forward is kept; ref gets no gradient (include/vrvq.h
+    vrvq_spectral_distance_grad)."""
+    return _ops().spectral_distance_grad(est, ref, lengths, [int(w) for w in windows],
+                                         [int(m) for m in n_mels], list(tables), list(bands),
+                                         list(weights), float(clamp_eps), float(pow),
+                                         float(log_weight), float(mag_weight), grad_distance)
+
+
 def resample(x: torch.Tensor, taps: torch.Tensor, first: torch.Tensor, old_rate: int, width: int,
              out_length: int) -> torch.Tensor:
     """x (rows, L) -> (rows, out_length) through the polyphase tap table taps (new, ntaps) /
@@ -583,6 +597,11 @@ def _register_fakes():
           log_weight, mag_weight):
         return (est.new_empty((est.shape[0], len(windows), 2), dtype=torch.float64),
                 est.new_empty((est.shape[0],), dtype=torch.float64))
+
+    @reg("vrvq::spectral_distance_grad")
+    def _(est, ref, lengths, windows, n_mels, tables, bands, weights, clamp_eps, pow,
+          log_weight, mag_weight, grad_distance):
+        return f32(est, (est.shape[0], est.shape[-1]))
 
     @reg("vrvq::resample")
     def _(x, taps, first, old_rate, width, out_length):

@@ -52,8 +52,10 @@ def unwrap(m: torch.nn.Module) -> torch.nn.Module:
 def build_state(generator: DAC_VRVQ, device: torch.device, ddp: bool = False,
                 discriminator: Optional[Discriminator] = None, lr: float = 1e-4,
                 betas=(0.8, 0.99), gamma: float = 0.999996,
-                mel_kwargs: Optional[dict] = None) -> State:
-    """scripts/train.py:138-229 without checkpoint resume / datasets."""
+                mel_kwargs: Optional[dict] = None, fused_losses: bool = False) -> State:
+    """scripts/train.py:138-229 without checkpoint resume / datasets. fused_losses computes the
+    STFT and mel losses and their gradients in the HIP kernels of utils.spectral_distance
+    (losses.py fused=True); the default is the torch composition."""
     gen = generator.to(device)
     disc = (discriminator or Discriminator()).to(device)
     if ddp:
@@ -66,7 +68,8 @@ def build_state(generator: DAC_VRVQ, device: torch.device, ddp: bool = False,
                  scheduler_g=torch.optim.lr_scheduler.ExponentialLR(opt_g, gamma),
                  discriminator=disc, optimizer_d=opt_d,
                  scheduler_d=torch.optim.lr_scheduler.ExponentialLR(opt_d, gamma),
-                 stft_loss=MultiScaleSTFTLoss(), mel_loss=MelSpectrogramLoss(**(mel_kwargs or {})),
+                 stft_loss=MultiScaleSTFTLoss(fused=fused_losses),
+                 mel_loss=MelSpectrogramLoss(**{"fused": fused_losses, **(mel_kwargs or {})}),
                  gan_loss=GANLoss(disc), waveform_loss=L1Loss())
 
 

@@ -321,6 +321,32 @@ def _per_scale(value, default, scales: int, what: str) -> list:
     return value
 
 
+class _SpectralDistance(torch.autograd.Function):
+    """ops.spectral_distance whose "distance" carries a gradient to est: the backward is
+    ops.spectral_distance_grad on the saved inputs (the spectra are recomputed; no host sync).
+    The terms are not differentiable and ref gets no gradient. The backward is differentiable
+    once only (once_differentiable: a double backward raises instead of treating the gradient as
+    a constant); lengths and the cached table tensors are constants of the call, kept on ctx."""
+
+    @staticmethod
+    def forward(ctx, e, r, lengths, windows, mels, tables, bands, weights, scalars):
+        terms, dist = ops.spectral_distance(e, r, lengths, windows, mels, tables, bands, weights,
+                                            *scalars)
+        ctx.save_for_backward(e, r)
+        ctx.args = (lengths, windows, mels, tables, bands, weights, scalars)
+        ctx.mark_non_differentiable(terms)
+        return terms, dist
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _grad_terms, grad_dist):
+        e, r = ctx.saved_tensors
+        lengths, windows, mels, tables, bands, weights, scalars = ctx.args
+        grad = ops.spectral_distance_grad(e, r, lengths, windows, mels, tables, bands, weights,
+                                          *scalars, grad_dist.to(torch.float64).contiguous())
+        return (grad,) + (None,) * 8
+
+
 def spectral_distance(est: torch.Tensor, ref: torch.Tensor, *, windows, n_mels=None,
                       clamp_eps: float = 1e-5, pow: float = 2.0, log_weight: float = 1.0,
                       mag_weight: float = 1.0, mel_fmin=None, mel_fmax=None,
@@ -337,7 +363,13 @@ def spectral_distance(est: torch.Tensor, ref: torch.Tensor, *, windows, n_mels=N
     signal_metrics; `windows` powers of two in [32, 2048]; `n_mels` one per window (0 or None: the
     linear bins); `lengths`, one per clip, measures each clip as if it ended there (a clip no
     longer than window / 2 gets NaN at that scale and in its distance). Returns "distance" (L, B),
-    "log" and "mag" (L, B, S), float64. Argument errors are ValueErrors before any launch."""
+    "log" and "mag" (L, B, S), float64. Argument errors are ValueErrors before any launch.
+
+    Where est requires a gradient (and grad mode is on), "distance" carries a grad_fn whose
+    backward is a HIP kernel too (ops.spectral_distance_grad: the spectra are recomputed, no
+    spectrogram is kept and there is no host sync); the forward's launch and bits are the same.
+    "log" and "mag" stay detached, and ref never receives a gradient, whether or not it requires
+    one. mel_distance and stft_distance inherit this."""
     windows = [int(w) for w in (windows if isinstance(windows, (list, tuple)) else [windows])]
     S = len(windows)
     if not 1 <= S <= 16:
@@ -363,8 +395,13 @@ def spectral_distance(est: torch.Tensor, ref: torch.Tensor, *, windows, n_mels=N
     lengths = _clip_lengths(lengths, B, e.device)
     tables, bands, weights = _spectral_device_tables(e.device, int(sample_rate), windows, mels,
                                                      fmin, fmax)
-    terms, dist = ops.spectral_distance(e, r, lengths, windows, mels, tables, bands, weights,
-                                        clamp_eps, pow, log_weight, mag_weight)
+    if e.requires_grad and torch.is_grad_enabled():
+        scalars = (float(clamp_eps), float(pow), float(log_weight), float(mag_weight))
+        terms, dist = _SpectralDistance.apply(e, r.detach(), lengths, windows, mels, tables, bands,
+                                              weights, scalars)
+    else:
+        terms, dist = ops.spectral_distance(e, r, lengths, windows, mels, tables, bands, weights,
+                                            clamp_eps, pow, log_weight, mag_weight)
     L = R // B
     return {"distance": dist.reshape(L, B), "log": terms[:, :, 0].reshape(L, B, S),
             "mag": terms[:, :, 1].reshape(L, B, S)}
