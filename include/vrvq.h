@@ -99,6 +99,11 @@ int vrvq_codebook_prep(const float* cb, int rows, int dim, float* cbn, float* c2
  * consumer of a conv output starts with a Snake). The consumer then runs with alpha == NULL,
  * so the activation is evaluated once per element instead of once per consumer tile. y may be
  * NULL when only the activated tensor is needed (it must not be NULL otherwise).
+ *
+ * Alignment: x, residual, y and y_snake must be 16-byte aligned (where a row length is a
+ * multiple of 4 the kernels move rows as 16-byte vectors and assume it); the same holds for
+ * vrvq_conv1d_ws, vrvq_conv1d_proj, vrvq_conv_transpose1d* and vrvq_residual_unit (x, x_snk, y,
+ * y_snake). The entry points do not check it.
  * ------------------------------------------------------------------------------------- */
 int vrvq_conv1d(const float* x, int batch, int cin, int tin, const float* alpha,
                 const float* inv_alpha, const float* w_packed, const uint16_t* w_x3, int cout,

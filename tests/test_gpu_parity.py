@@ -344,10 +344,11 @@ def test_conv1d_x3_vs_torch(case):
                                   (2, 256, 512, 700, 1, 1, 0, 1, True, True, 0),
                                   (2, 96, 128, 600, 1, 1, 0, 1, False, True, 0)])
 def test_conv1d_x3_long_rows_vs_torch(case):
-    """x3 convs over long rows: k7 over rows of >= 640 samples with >= 128 output channels and
-    Cin % 16 == 0 (the pair-chunk 64 x 256 tiles of conv_x3.h; dispatch_tiles takes them only
-    for such Cin, so launch_cfg's pair_ok guard is defensive), the k1 + skip GEMMs on their
-    8-channel chunks, and ragged last tiles."""
+    """x3 convs over long rows, as vrvq_conv_plan places them: the three k7 cases (rows of >= 640
+    samples, >= 128 output channels, Cin % 16 == 0) run the pair-chunk 64 x 256 tiles of
+    conv_x3.h (dispatch_tiles takes them only for such Cin; launch_cfg runs a pair tile on plain
+    chunks for any other), the k1 + skip GEMMs run 192 x 64, 128 x 64 and 128 x 128 tiles on
+    plain 32-channel chunks; every case ends in a ragged last tile."""
     test_conv1d_x3_vs_torch(case)
 
 
