@@ -732,6 +732,55 @@ int vrvq_unpack_codes(const uint16_t* packed, const int* counts, const long long
                       int batch, int nq, int frames, int64_t* codes, float* mask,
                       vrvq_stream_t stream);
 
+/* Bitstream ("VRVQ bitstream 1"): the bit-granular, parallel-decodable form of the stream above.
+ * A stream is an array of little-endian uint32 words; a field of width n at bit position p puts
+ * bit j of its value at stream bit p + j, and stream bit q is bit q & 31 of word q >> 5 (a field
+ * may straddle two words). Fields: a code takes w = max(1, ceil(log2(ncode))) bits (ncode in
+ * [2, 65536]), a count cb = ceil(log2(nq + 1)) bits; count_bits = 0 is the fixed-count stream
+ * (every frame keeps all nq stages, mask = NULL, no plane A). Row r (a clip) is two planes:
+ *   A  frames count fields c_t = sum_i mask[r][i][t], t ascending, zero-padded to a whole word
+ *   B  for t ascending, i < c_t: codes[r][i][t]; the field of (t, i) starts at bit
+ *      w * (sum_{t' < t} c_t' + i) of the plane; zero-padded to a whole word
+ * so row_words[r] = ceil(frames * cb / 32) + ceil(w * sum_t c_t / 32); rows are concatenated,
+ * row_off[r] = sum_{r' < r} row_words[r'] (rows + 1 entries). A row's words do not depend on the
+ * other rows. Both directions run on a grid of (chunk of VRVQ_BITSTREAM_CHUNK_FRAMES frames, row);
+ * chunk_total / chunk_off hold rows * ceil(frames / VRVQ_BITSTREAM_CHUNK_FRAMES) entries (codes
+ * of a chunk; codes of the row before the chunk). *err must be zero on entry and receives the
+ * largest code raised. Limits: nq <= 255, frames <= 2^24, rows * chunks < 2^31.
+ *   vrvq_bitpack_plan    codes, mask -> counts [rows*frames], chunk_total, chunk_off, row_codes
+ *                        [rows] (sum_t c_t), row_words [rows], row_off [rows + 1]; *err = 1: a
+ *                        mask column is not prefix-shaped; 2: a kept code outside [0, ncode)
+ *   vrvq_bitpack_write   zeroes words[0 .. total_words) and writes both planes of every row
+ *                        (total_words = row_off[rows], read by the caller); the words are a pure
+ *                        function of codes and mask
+ *   vrvq_bitunpack_plan  reads plane A within the header's row_words (row_off [rows + 1] = their
+ *                        exclusive scan, made by the caller from the header: a corrupt row
+ *                        cannot move the others; row_off[rows] <= total_words) -> counts,
+ *                        chunk_total, chunk_off, row_err [rows] (zero on entry, like *err);
+ *                        *err = 3: a count above nq; 4: a row whose counts give another word
+ *                        count than row_off[r + 1] - row_off[r], or leave the row
+ *   vrvq_bitunpack_read  -> codes [rows][nq][frames] int64 (0 where masked) and mask (or NULL);
+ *                        *err = 2: a decoded value >= ncode. A row flagged by the plan decodes
+ *                        to zeros; no word outside [0, total_words) or the row is ever read. */
+#define VRVQ_BITSTREAM_CHUNK_FRAMES 256
+int vrvq_bitstream_chunk_frames(void);
+int vrvq_bitpack_plan(const int64_t* codes, const float* mask, int rows, int nq, int frames,
+                      int ncode, int* counts, int* chunk_total, long long* chunk_off,
+                      long long* row_codes, long long* row_words, long long* row_off, int* err,
+                      vrvq_stream_t stream);
+int vrvq_bitpack_write(const int64_t* codes, const int* counts, const long long* chunk_off,
+                       const long long* row_off, int rows, int nq, int frames, int ncode,
+                       int count_bits, uint32_t* words, long long total_words,
+                       vrvq_stream_t stream);
+int vrvq_bitunpack_plan(const uint32_t* words, long long total_words, const long long* row_off,
+                        int rows, int nq, int frames, int ncode, int count_bits, int* counts,
+                        int* chunk_total, long long* chunk_off, int* row_err, int* err,
+                        vrvq_stream_t stream);
+int vrvq_bitunpack_read(const uint32_t* words, long long total_words, const int* counts,
+                        const long long* chunk_off, const long long* row_off, const int* row_err,
+                        int rows, int nq, int frames, int ncode, int count_bits, int64_t* codes,
+                        float* mask, int* err, vrvq_stream_t stream);
+
 /* ResidualVectorQuantize.from_latents (models/quantize.py:251-285): per stage i < nq the
  * nearest normalised codeword of the stage's own latent latents[b][8i..8i+8][t] (decode_latents,
  * :87-103; the distance expression of vrvq_rvq_chain) -> codes [B][nq][T] int64. latents has

@@ -13,6 +13,8 @@ from .utils import (cal_bpf_from_mask, cal_bpf_tensor, check_errors, generate_ma
                     mel_distance, rd_sweep, scale_importance, signal_metrics, solve_levels,
                     solve_quality, spectral_distance, stft_distance)
 from .resampling import resample
+from .codes_io import (Bitstream, DACFile, VRVQFile, pack_bitstream, pack_codes, unpack_bitstream,
+                       unpack_codes)
 from .metering import loudness, normalize_loudness
 from .config import from_config, load_config, model_kwargs
 
@@ -25,4 +27,6 @@ __all__ = [
     "from_config", "check_errors", "rate_curve", "solve_levels", "kbps_to_budget",
     "signal_metrics", "rd_sweep", "solve_quality", "spectral_distance", "mel_distance",
     "stft_distance", "resample", "loudness", "normalize_loudness",
+    "Bitstream", "DACFile", "VRVQFile", "pack_bitstream", "unpack_bitstream", "pack_codes",
+    "unpack_codes",
 ]

@@ -88,6 +88,11 @@ SIGNATURES = {
     "vrvq_pack_codes": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "vrvq_unpack_offsets": [_P, _I, _I, _P, _P, _P],
     "vrvq_unpack_codes": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "vrvq_bitpack_plan": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "vrvq_bitpack_write": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P],
+    "vrvq_bitunpack_plan": [_P, ctypes.c_longlong, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "vrvq_bitunpack_read": [_P, ctypes.c_longlong, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P,
+                            _P],
     "vrvq_rvq_nearest": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P],
     # training step
     "vrvq_wgrad_plan": [_I, _I, _I, _I, _I, _P, _P],
@@ -115,13 +120,15 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_rvq_debug_capacity": ([_I], _I), "vrvq_conv_last_launch": ([_P], _I),
          "vrvq_conv_plan": ([_I] * 11 + [_P], _I),
          "vrvq_resample_error": ([], ctypes.c_char_p),
-         "vrvq_loudness_error": ([], ctypes.c_char_p)}
+         "vrvq_loudness_error": ([], ctypes.c_char_p),
+         "vrvq_bitstream_chunk_frames": ([], _I)}
 
 METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
 SPECTRAL_TILE_SAMPLES = 8192  # VRVQ_SPECTRAL_TILE_SAMPLES (tests/test_spectral.py compares)
 RESAMPLE_TILE = 512  # VRVQ_RESAMPLE_TILE (tests/test_resample.py compares)
 LOUDNESS_CHUNK = 256  # VRVQ_LOUDNESS_CHUNK (tests/test_loudness.py compares)
 LOUDNESS_PLAN_LEN = 30  # VRVQ_LOUDNESS_PLAN_LEN
+BITSTREAM_CHUNK_FRAMES = 256  # VRVQ_BITSTREAM_CHUNK_FRAMES (tests/test_bitstream.py compares)
 
 
 def spectral_tile_frames(window: int) -> int:

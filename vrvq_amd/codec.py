@@ -38,6 +38,13 @@ What the reference body does, and how it runs here:
   (scripts/inference.py:99-100). The importance subnet keeps its "same" padding in padding=False
   mode (the reference's setter would shrink imp_map by 12 frames against z and fail at
   models/quantize.py:421).
+* containers: `container="dac"` (default) is that DACFile, 16 bits for every stage of every
+  frame whatever the level. `container="vrvq"` writes the same codes and mask as a bit-granular
+  stream (codes_io.VRVQFile, include/vrvq.h "Bitstream"): the kept codes at their exact width
+  plus one count per frame, packed on the device by the HIP bit packer, so that only the words
+  and the loudness reach the host; with target_kbps the count plane is part of the budget.
+  decompress takes either container (by type, or by the file's magic) and decodes them with the
+  same kernels from the same codes.
 """
 from __future__ import annotations
 
@@ -50,7 +57,8 @@ from typing import Optional, Union
 import numpy as np
 import torch
 
-from .codes_io import SUPPORTED_VERSIONS, DACFile
+from .codes_io import (SUPPORTED_VERSIONS, DACFile, VRVQFile, count_bits_of, is_vrvq_file,
+                       pack_bitstream)
 
 MIN_LOUDNESS = -70.0
 GAIN_FACTOR = math.log(10) / 20
@@ -211,8 +219,13 @@ def _as_signal(obj, sample_rate) -> AudioSignal:
 def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
              verbose: bool = False, normalize_db: Optional[float] = -16,
              n_quantizers: Optional[int] = None, level: float = 1.0, max_batch: int = 64,
-             sample_rate: Optional[int] = None, target_kbps: Optional[float] = None) -> DACFile:
+             sample_rate: Optional[int] = None, target_kbps: Optional[float] = None,
+             container: str = "dac") -> Union[DACFile, VRVQFile]:
     """models/dac_base.py:162-240 on the HIP encode path (see the module docstring).
+
+    `container`: "dac" (a DACFile) or "vrvq" (a VRVQFile: the same codes, bit-packed on the
+    device). With "vrvq" and target_kbps the solver also budgets the stream's count field of
+    every frame, so that count plane + code plane of the whole file fit target_kbps.
 
     `target_kbps` (VBR models) replaces `level`: the windows are encoded once, and one level for
     the whole file -- the largest in the model's [level_min, level_max] at which all windows
@@ -221,7 +234,7 @@ def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
     depend on the level: only the masks are built from it, there is no second encode, and the
     file equals compress(level=solve_file_level(...))."""
     return _compress(model, audio_path_or_signal, False, win_duration, verbose, normalize_db,
-                     n_quantizers, level, max_batch, sample_rate, target_kbps)
+                     n_quantizers, level, max_batch, sample_rate, target_kbps, container)
 
 
 def solve_file_level(model, audio, target_kbps: float, **compress_kw) -> float:
@@ -233,7 +246,10 @@ def solve_file_level(model, audio, target_kbps: float, **compress_kw) -> float:
 @torch.no_grad()
 def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose=False,
               normalize_db=-16, n_quantizers=None, level=1.0, max_batch=64, sample_rate=None,
-              target_kbps=None):
+              target_kbps=None, container="dac"):
+    if container not in ("dac", "vrvq"):
+        raise ValueError(f"compress: container must be 'dac' or 'vrvq', not {container!r}")
+    packed = container == "vrvq"
     vbr = getattr(model, "model_type", "CBR") == "VBR"
     if target_kbps is not None:
         if not vbr:
@@ -284,7 +300,7 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
             x = audio[..., i:i + n_samples]
             clips.append(torch.nn.functional.pad(x, (0, n_samples - x.shape[-1])))
         clips = torch.cat(clips, 0)                          # (n_win * nb*nac, 1, n_samples)
-        codes, imps = [], []
+        codes, imps, masks = [], [], []
         for c0 in range(0, clips.shape[0], max_batch):
             x = model.preprocess(clips[c0:c0 + max_batch].contiguous(), model.sample_rate)
             if target_kbps is not None:  # codes and imp_map do not depend on the level
@@ -293,7 +309,11 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
                 imps.append(out["imp_map"])
             elif vbr and n_quantizers is None:
                 out = model.encode(x, None, level, want_z_q_is=False)
-                c = out["codes"].masked_fill(out["mask_imp"] == 0, model.codebook_size)
+                if packed:  # the stream takes codes and mask apart
+                    c = out["codes"]
+                    masks.append(out["mask_imp"])
+                else:
+                    c = out["codes"].masked_fill(out["mask_imp"] == 0, model.codebook_size)
             else:
                 out = model.encode(x, n_quantizers) if not vbr else \
                     model.encode(x, n_quantizers, level, want_z_q_is=False)
@@ -302,6 +322,8 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
             if verbose:
                 print(f"[compress] windows {c0}..{c0 + x.shape[0]} of {clips.shape[0]}")
         codes = torch.cat(codes, 0)                          # (n_win * nb*nac, Nq, frames)
+        mask = torch.cat(masks, 0) if masks else None
+        file_level = None
         if target_kbps is not None:
             from . import utils
             imp = torch.cat(imps, 0)
@@ -309,7 +331,8 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
             lv, _, status = utils.solve_levels(
                 imp, target_kbps, nq=nq, sample_rate=model.sample_rate,
                 hop_length=model.hop_length, level_min=model.quantizer.level_min,
-                level_max=model.quantizer.level_max, pooled=True)
+                level_max=model.quantizer.level_max, pooled=True,
+                side_bits_per_frame=count_bits_of(nq) if packed else 0)
             if int(status.item()) == 1:
                 raise ValueError(f"compress: {target_kbps} kbps is below the file's rate at "
                                  f"level_min = {model.quantizer.level_min}")
@@ -317,13 +340,25 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
             if level_only:
                 return file_level
             mask = utils.generate_mask_hard(utils.scale_importance(imp, file_level, float(nq)), nq)
-            codes = codes.masked_fill(mask == 0, model.codebook_size)
+            if not packed:
+                codes = codes.masked_fill(mask == 0, model.codebook_size)
         elif level_only:
             raise ValueError("solve_file_level: target_kbps is required")
         chunk_length = codes.shape[-1]
         nw = len(starts)
         codes = codes.reshape(nw, nb * nac, codes.shape[1], chunk_length)
         codes = codes.permute(1, 2, 0, 3).reshape(nb * nac, -1, nw * chunk_length)
+        if packed:
+            if mask is not None:
+                mask = mask.reshape(nw, nb * nac, mask.shape[1], chunk_length)
+                mask = mask.permute(1, 2, 0, 3).reshape(nb * nac, -1, nw * chunk_length)
+            bs = pack_bitstream(codes, mask, model.codebook_size).to("cpu")
+            return VRVQFile(bitstream=bs, chunk_length=chunk_length,
+                            original_length=original_length, input_db=input_db.cpu(),
+                            channels=nac, sample_rate=original_sr, padding=model.padding,
+                            level=file_level if target_kbps is not None else
+                            (float(level) if mask is not None else None),
+                            target_kbps=None if target_kbps is None else float(target_kbps))
         dac = DACFile(codes=codes.cpu(), chunk_length=chunk_length,
                       original_length=original_length, input_db=input_db.cpu(), channels=nac,
                       sample_rate=original_sr, padding=model.padding,
@@ -334,17 +369,26 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
 
 
 @torch.no_grad()
-def decompress(model, obj: Union[str, Path, DACFile], verbose: bool = False,
+def decompress(model, obj: Union[str, Path, DACFile, VRVQFile], verbose: bool = False,
                max_batch: int = 64) -> AudioSignal:
-    """models/dac_base.py:265-304 on the HIP from_codes + decode path."""
+    """models/dac_base.py:265-304 on the HIP from_codes + decode path. obj: a DACFile, a
+    VRVQFile, or a path to either (told apart by the file's magic). A VRVQFile's stream is
+    unpacked on the device into the codes its DACFile form would hold."""
     model.eval()
     if isinstance(obj, (str, Path)):
-        obj = DACFile.load(obj)
+        obj = VRVQFile.load(obj) if is_vrvq_file(obj) else DACFile.load(obj)
     original_padding = model.padding
     dev = model.device
     try:
         model.padding = bool(obj.padding)
-        codes = obj.codes.to(dev)
+        if isinstance(obj, VRVQFile):
+            if obj.bitstream.codebook_size != model.codebook_size:
+                raise ValueError(f"decompress: the stream's codebook_size "
+                                 f"{obj.bitstream.codebook_size} is not the model's "
+                                 f"{model.codebook_size}")
+            codes = obj.marker_codes(dev)
+        else:
+            codes = obj.codes.to(dev)
         n_items, nq, total = codes.shape
         cl = obj.chunk_length
         starts = list(range(0, total, cl))

@@ -981,6 +981,126 @@ std::tuple<Tensor, Tensor> unpack_codes(const Tensor& packed, const Tensor& coun
   return {codes, mask};
 }
 
+// --------------------------------------------------------------------------- bitstream
+// "VRVQ bitstream 1" (include/vrvq.h "Bitstream"): bit-granular packing of the codes a
+// prefix-shaped mask keeps. The stream's length is data-dependent: bitpack_plan leaves it in
+// info, which the caller reads once (vrvq_amd/codes_io.py pack_bitstream).
+// info (int64, 3 R + 2): row_off [R + 1] | row_codes [R] | row_words [R] | err (low int32).
+std::tuple<Tensor, Tensor, Tensor> bitpack_plan(const Tensor& codes, const optional<Tensor>& mask,
+                                                int64_t ncode) {
+  check_t(codes, "codes", at::kLong);
+  TORCH_CHECK(codes.dim() == 3, "bitpack_plan: codes must be (R, Nq, T)");
+  if (mask.has_value()) {
+    check_on(*mask, codes, "mask");
+    TORCH_CHECK(mask->sizes() == codes.sizes(), "bitpack_plan: mask must have codes' shape");
+  }
+  c10::DeviceGuard guard(codes.device());
+  const int64_t R = codes.size(0), nq = codes.size(1), T = codes.size(2);
+  TORCH_CHECK(R > 0 && nq > 0 && T > 0 && R < (1 << 30) && T <= (1 << 24),
+              "bitpack_plan: unsupported shape");
+  const int64_t nchunk = (T + VRVQ_BITSTREAM_CHUNK_FRAMES - 1) / VRVQ_BITSTREAM_CHUNK_FRAMES;
+  Tensor counts = at::empty({R, T}, codes.options().dtype(at::kInt));
+  Tensor chunk_total = at::empty({R, nchunk}, codes.options().dtype(at::kInt));
+  Tensor chunk_off = at::empty({R, nchunk}, codes.options());
+  Tensor info = at::zeros({3 * R + 2}, codes.options());
+  long long* ip = reinterpret_cast<long long*>(info.data_ptr<int64_t>());
+  check_rc(vrvq_bitpack_plan(codes.data_ptr<int64_t>(),
+                             mask.has_value() ? mask->data_ptr<float>() : nullptr, (int)R, (int)nq,
+                             (int)T, (int)ncode, counts.data_ptr<int>(),
+                             chunk_total.data_ptr<int>(),
+                             reinterpret_cast<long long*>(chunk_off.data_ptr<int64_t>()),
+                             ip + R + 1, ip + 2 * R + 1, ip, reinterpret_cast<int*>(ip + 3 * R + 1),
+                             stream_of(codes)),
+           "vrvq_bitpack_plan");
+  return {counts, chunk_off, info};
+}
+
+Tensor bitpack_write(const Tensor& codes, const Tensor& counts, const Tensor& chunk_off,
+                     const Tensor& info, int64_t total_words, int64_t ncode, int64_t count_bits) {
+  check_t(codes, "codes", at::kLong);
+  check_on(counts, codes, "counts", at::kInt);
+  check_on(chunk_off, codes, "chunk_off", at::kLong);
+  check_on(info, codes, "info", at::kLong);
+  TORCH_CHECK(codes.dim() == 3, "bitpack_write: codes must be (R, Nq, T)");
+  const int64_t R = codes.size(0), nq = codes.size(1), T = codes.size(2);
+  const int64_t nchunk = (T + VRVQ_BITSTREAM_CHUNK_FRAMES - 1) / VRVQ_BITSTREAM_CHUNK_FRAMES;
+  TORCH_CHECK(counts.numel() == R * T && chunk_off.numel() == R * nchunk &&
+                  info.numel() == 3 * R + 2 && total_words >= 0,
+              "bitpack_write: plan tensors do not match codes");
+  c10::DeviceGuard guard(codes.device());
+  Tensor words = at::empty({total_words}, codes.options().dtype(at::kInt));
+  if (total_words > 0)
+    check_rc(vrvq_bitpack_write(codes.data_ptr<int64_t>(), counts.data_ptr<int>(),
+                                reinterpret_cast<const long long*>(chunk_off.data_ptr<int64_t>()),
+                                reinterpret_cast<const long long*>(info.data_ptr<int64_t>()),
+                                (int)R, (int)nq, (int)T, (int)ncode, (int)count_bits,
+                                reinterpret_cast<uint32_t*>(words.data_ptr<int>()),
+                                (long long)total_words, stream_of(codes)),
+             "vrvq_bitpack_write");
+  return words;
+}
+
+// row_off (int64, R + 1): the exclusive scan of the header's row_words, made on the host.
+// flags (int32, R + 2): row_err [R] | the plan's err | bitunpack_read's err.
+std::tuple<Tensor, Tensor, Tensor> bitunpack_plan(const Tensor& words, const Tensor& row_off,
+                                                  int64_t nq, int64_t frames, int64_t ncode,
+                                                  int64_t count_bits) {
+  check_t(words, "words", at::kInt);
+  check_on(row_off, words, "row_off", at::kLong);
+  TORCH_CHECK(words.dim() == 1 && row_off.dim() == 1 && row_off.numel() > 1,
+              "bitunpack_plan: words 1-D, row_off (R + 1,)");
+  c10::DeviceGuard guard(words.device());
+  const int64_t R = row_off.numel() - 1, T = frames;
+  TORCH_CHECK(R < (1 << 30) && T > 0 && T <= (1 << 24) && nq > 0 && nq <= 255,
+              "bitunpack_plan: unsupported shape");
+  const int64_t nchunk = (T + VRVQ_BITSTREAM_CHUNK_FRAMES - 1) / VRVQ_BITSTREAM_CHUNK_FRAMES;
+  Tensor counts = at::empty({R, T}, words.options());
+  Tensor chunk_total = at::empty({R, nchunk}, words.options());
+  Tensor chunk_off = at::empty({R, nchunk}, row_off.options());
+  Tensor flags = at::zeros({R + 2}, words.options());
+  check_rc(vrvq_bitunpack_plan(
+               words.numel() ? reinterpret_cast<const uint32_t*>(words.data_ptr<int>()) : nullptr,
+               (long long)words.numel(),
+               reinterpret_cast<const long long*>(row_off.data_ptr<int64_t>()), (int)R, (int)nq,
+               (int)T, (int)ncode, (int)count_bits, counts.data_ptr<int>(),
+               chunk_total.data_ptr<int>(),
+               reinterpret_cast<long long*>(chunk_off.data_ptr<int64_t>()), flags.data_ptr<int>(),
+               flags.data_ptr<int>() + R, stream_of(words)),
+           "vrvq_bitunpack_plan");
+  return {counts, chunk_off, flags};
+}
+
+// Writes its error code into flags[R + 1] (flags is the plan's, mutated).
+std::tuple<Tensor, Tensor> bitunpack_read(const Tensor& words, const Tensor& counts,
+                                          const Tensor& chunk_off, const Tensor& row_off,
+                                          Tensor& flags, int64_t nq, int64_t ncode,
+                                          int64_t count_bits) {
+  check_t(words, "words", at::kInt);
+  check_on(counts, words, "counts", at::kInt);
+  check_on(chunk_off, words, "chunk_off", at::kLong);
+  check_on(row_off, words, "row_off", at::kLong);
+  check_on(flags, words, "flags", at::kInt);
+  TORCH_CHECK(words.dim() == 1 && counts.dim() == 2, "bitunpack_read: words 1-D, counts (R, T)");
+  const int64_t R = counts.size(0), T = counts.size(1);
+  const int64_t nchunk = (T + VRVQ_BITSTREAM_CHUNK_FRAMES - 1) / VRVQ_BITSTREAM_CHUNK_FRAMES;
+  TORCH_CHECK(R > 0 && T > 0 && chunk_off.numel() == R * nchunk && row_off.numel() == R + 1 &&
+                  flags.numel() == R + 2 && nq > 0 && nq <= 255,
+              "bitunpack_read: plan tensors do not match");
+  c10::DeviceGuard guard(words.device());
+  Tensor codes = at::empty({R, nq, T}, row_off.options());
+  Tensor mask = empty_f({R, nq, T}, words);
+  check_rc(vrvq_bitunpack_read(
+               words.numel() ? reinterpret_cast<const uint32_t*>(words.data_ptr<int>()) : nullptr,
+               (long long)words.numel(), counts.data_ptr<int>(),
+               reinterpret_cast<const long long*>(chunk_off.data_ptr<int64_t>()),
+               reinterpret_cast<const long long*>(row_off.data_ptr<int64_t>()),
+               flags.data_ptr<int>(), (int)R, (int)nq, (int)T, (int)ncode, (int)count_bits,
+               codes.data_ptr<int64_t>(), mask.data_ptr<float>(), flags.data_ptr<int>() + R + 1,
+               stream_of(words)),
+           "vrvq_bitunpack_read");
+  return {codes, mask};
+}
+
 // --------------------------------------------------------------------------- training step
 // Backward operators of the generator (scripts/train.py:262-330), used by
 // the torch.autograd.Functions of vrvq_amd/train.py.
@@ -1439,6 +1559,16 @@ TORCH_LIBRARY(vrvq, m) {
   m.def(
       "unpack_codes(Tensor packed, Tensor counts, Tensor clip_off, int n_codebooks) "
       "-> (Tensor, Tensor)");
+  m.def("bitpack_plan(Tensor codes, Tensor? mask, int ncode) -> (Tensor, Tensor, Tensor)");
+  m.def(
+      "bitpack_write(Tensor codes, Tensor counts, Tensor chunk_off, Tensor info, int total_words, "
+      "int ncode, int count_bits) -> Tensor");
+  m.def(
+      "bitunpack_plan(Tensor words, Tensor row_off, int nq, int frames, int ncode, "
+      "int count_bits) -> (Tensor, Tensor, Tensor)");
+  m.def(
+      "bitunpack_read(Tensor words, Tensor counts, Tensor chunk_off, Tensor row_off, "
+      "Tensor(a!) flags, int nq, int ncode, int count_bits) -> (Tensor, Tensor)");
   m.def(
       "conv1d_wgrad(Tensor a, Tensor x, int k, int stride, int pad, int dil, Tensor? alpha_a, "
       "Tensor? inv_alpha_a, Tensor? alpha, Tensor? inv_alpha) -> Tensor");
@@ -1507,6 +1637,10 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("pack_codes", &pack_codes); \
   m.impl("unpack_offsets", &unpack_offsets); \
   m.impl("unpack_codes", &unpack_codes); \
+  m.impl("bitpack_plan", &bitpack_plan); \
+  m.impl("bitpack_write", &bitpack_write); \
+  m.impl("bitunpack_plan", &bitunpack_plan); \
+  m.impl("bitunpack_read", &bitunpack_read); \
   m.impl("conv1d_wgrad", &conv1d_wgrad); \
   m.impl("snake_backward", &snake_backward); \
   m.impl("bias_grad", &bias_grad); \

@@ -637,6 +637,32 @@ def _register_fakes():
         return (counts.new_empty((B, n_codebooks, T), dtype=torch.int64),
                 counts.new_empty((B, n_codebooks, T), dtype=torch.float32))
 
+    @reg("vrvq::bitpack_plan")
+    def _(codes, mask, ncode):
+        R, _nq, T = codes.shape
+        nchunk = -(-T // 256)
+        return (codes.new_empty((R, T), dtype=torch.int32),
+                codes.new_empty((R, nchunk), dtype=torch.int64),
+                codes.new_empty((3 * R + 2,), dtype=torch.int64))
+
+    @reg("vrvq::bitpack_write")
+    def _(codes, counts, chunk_off, info, total_words, ncode, count_bits):
+        return codes.new_empty((total_words,), dtype=torch.int32)
+
+    @reg("vrvq::bitunpack_plan")
+    def _(words, row_off, nq, frames, ncode, count_bits):
+        R = row_off.shape[0] - 1
+        nchunk = -(-frames // 256)
+        return (words.new_empty((R, frames), dtype=torch.int32),
+                words.new_empty((R, nchunk), dtype=torch.int64),
+                words.new_empty((R + 2,), dtype=torch.int32))
+
+    @reg("vrvq::bitunpack_read")
+    def _(words, counts, chunk_off, row_off, flags, nq, ncode, count_bits):
+        R, T = counts.shape
+        return (words.new_empty((R, nq, T), dtype=torch.int64),
+                words.new_empty((R, nq, T), dtype=torch.float32))
+
     @reg("vrvq::conv1d_wgrad")
     def _(a, x, k, stride, pad, dil, alpha_a, inv_alpha_a, alpha, inv_alpha):
         return f32(a, (a.shape[1], x.shape[1], k))

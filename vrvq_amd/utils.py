@@ -102,15 +102,29 @@ def kbps_to_budget(kbps: float, frames: int, sample_rate: int, hop_length: int) 
     return int(math.floor(float(kbps) * 1000 / math.floor(sample_rate / hop_length) * frames))
 
 
+def net_budgets(budgets, frames: int, side_bits_per_frame: int = 0):
+    """Bit budgets of groups of `frames` frames after frames * side_bits_per_frame bits of side
+    information. May be negative: no level fits (solve_levels status 1)."""
+    side = int(side_bits_per_frame)
+    if side < 0 or side != side_bits_per_frame:
+        raise ValueError("side_bits_per_frame must be a non-negative integer")
+    return [int(b) - int(frames) * side for b in budgets]
+
+
 def solve_levels(imp_map: torch.Tensor, target_kbps, *, nq: int, sample_rate: int,
                  hop_length: int, level_min: float, level_max: float, bits_per_codebook=10,
-                 pooled: bool = False):
+                 pooled: bool = False, side_bits_per_frame: int = 0):
     """The largest level in [level_min, level_max] at which each clip (or, pooled, the whole
     batch as one group) stays within `target_kbps`, solved on the device in one launch
     (include/vrvq.h vrvq_rate_solve). target_kbps: a number, or one per clip (not pooled).
     Returns device tensors (levels (G,) float32, bpf (G,) float32, status (G,) int32; 0 solved,
     1 infeasible even at level_min, 2 level_max fits), G = B, or 1 when pooled. No host sync for
-    a number or a host sequence."""
+    a number or a host sequence.
+
+    side_bits_per_frame: bits every frame spends outside its codes (the count field of the
+    bitstream container, codes_io.count_bits_of(nq)); frames * side_bits_per_frame are taken off
+    each group's budget on the host before the solve, so codes + side information fit
+    target_kbps. A budget that goes negative gives status 1. The returned bpf counts codes only."""
     imp = _imp_rows(imp_map)
     B, T = imp.shape
     if level_min is None or level_max is None:
@@ -129,7 +143,8 @@ def solve_levels(imp_map: torch.Tensor, target_kbps, *, nq: int, sample_rate: in
             raise ValueError(f"solve_levels: {len(ks)} targets for {B} clips")
         budgets, frames = [kbps_to_budget(k, T, sample_rate, hop_length) for k in ks], T
         off = torch.arange(B + 1, dtype=torch.int32, device=imp.device)
-    budget = _device_const(budgets, torch.int64, imp.device)
+    budget = _device_const(net_budgets(budgets, frames, side_bits_per_frame), torch.int64,
+                           imp.device)
     levels, total, status = ops.rate_solve(imp, _bits_table(bits_per_codebook, nq, imp.device),
                                            off, budget, level_min, level_max)
     return levels, (total.to(torch.float64) / frames).to(torch.float32), status
