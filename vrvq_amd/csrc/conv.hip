@@ -883,6 +883,7 @@ int run_conv1d(ConvArgs a, int batch, int cin, int tin, int cout, int cout_pad, 
   if (stride > 1 && (stride & (stride - 1)) == 0)
     while ((1 << a.ssh) < stride) ++a.ssh;
   a.ylen = tout; a.epi = epilogue;
+  if (a.w3 != nullptr && !x3_offsets_fit(tin, cout_pad)) return VRVQ_ERR_UNSUPPORTED;
   if (workspace != nullptr) {
     long long need = 0;
     const int rc = vrvq_conv1d_workspace(batch, cin, tin, cout, k, stride, pad, dil,
@@ -920,6 +921,7 @@ int run_conv_transpose1d(ConvArgs a, int batch, int cin, int tin, int cout, int 
   // pad 0 = the padding=False windows of the chunked codec (models/dac_base.py:72-82)
   VRVQ_CHECK_ARG(pad >= 0 && pad < stride);
   VRVQ_CHECK_ARG(cout_pad >= cout * stride && cout_pad % 64 == 0);
+  if (a.w3 != nullptr && !x3_offsets_fit(tin, cout_pad)) return VRVQ_ERR_UNSUPPORTED;
   a.cin = cin; a.tin = tin; a.M = cout * stride; a.m_pad = cout_pad; a.cout = cout;
   a.stride = 1; a.pad = 1; a.dil = 1; a.ng = tin + 1; a.up = stride; a.up_pad = pad;
   a.ylen = (tin - 1) * stride - 2 * pad + 2 * stride;

@@ -134,14 +134,20 @@ void ru_fused_kernel(RuArgs ra) {
           for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
       constexpr int NQ = BM / 16;
       const u32x4* hs = reinterpret_cast<const u32x4*>(hsb);
+      // global octet o = 2 q + lh of the k = 1 packing (chunks of 4 octets, three planes each):
+      // w1x3[((o >> 2) * 3 + p) * 4 + (o & 3)) * m_pad + row]. The thread's part (its lane
+      // half's octet, its row) is one 32-bit byte offset; the step / plane / row-block term is
+      // uniform and stays in scalar registers.
+      const unsigned wlo = ((unsigned)lh * (unsigned)a.m_pad + (unsigned)(wm * TM + lr)) * 16u;
       auto lda = [&](int q, u32x4 (&av)[3][RM]) {
-        const int o = 2 * q + lh;  // global octet; k = 1 packing: chunks of 4 octets
-        const int ch = o >> 2, oo = o & 3;
+        const u32x4* wq = ra.w1x3 + (size_t)((q >> 1) * 12 + 2 * (q & 1)) * a.m_pad;
+        const unsigned wl = x3_opaque(wlo);  // scalar base + register: conv_x3.h
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
           for (int i = 0; i < RM; ++i)
-            av[p][i] = ra.w1x3[((size_t)(ch * 3 + p) * 4 + oo) * a.m_pad + wm * TM + i * 32 + lr];
+            av[p][i] = *reinterpret_cast<const u32x4*>(
+                reinterpret_cast<const char*>(wq + (size_t)(p * 4) * a.m_pad + i * 32) + wl);
       };
       u32x4 an[3][RM];
       lda(0, an);
@@ -235,6 +241,8 @@ void ru_fused_kernel(RuArgs ra) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
       const u32x4* hs = reinterpret_cast<const u32x4*>(hsb);
+      // (The index stays in vector arithmetic here: with the scalar-base form of the planes
+      // above, this kernel, at its 256-register limit, spills 184 instead of 160 bytes per lane.)
       auto lda = [&](int q, u32x4 (&av)[3][RM]) {
         const int o = 2 * q + lh;  // global octet; k = 1 packing: chunks of 4 octets
         const int ch = o >> 2, oo = o & 3;
@@ -428,6 +436,7 @@ extern "C" int vrvq_residual_unit(const float* x, const float* x_snk, int batch,
   VRVQ_CHECK_ARG(y_snake == nullptr || (alpha_out && inv_alpha_out));
   VRVQ_CHECK_ARG(batch > 0 && channels > 0 && frames > 0 && dil >= 1 && dil <= 9);
   VRVQ_CHECK_ARG(cout_pad >= channels && cout_pad % 128 == 0);
+  if (w7_x3 != nullptr && !x3_offsets_fit(frames, cout_pad)) return VRVQ_ERR_UNSUPPORTED;
   RuArgs ra{};
   ConvArgs& p = ra.p1;
   p.x = x_snk; p.alpha = nullptr; p.inv_alpha = nullptr; p.w = w7_packed; p.bias = nullptr;

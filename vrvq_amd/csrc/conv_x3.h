@@ -86,6 +86,13 @@ __device__ __forceinline__ void split3x2(float v0, float v1, unsigned& h, unsign
   l = __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf16x2));
 }
 
+// A value the optimiser cannot see through: keeps what is derived from it where it is written
+// (conv_mainloop_x3's refill offsets). No instruction.
+__device__ __forceinline__ unsigned x3_opaque(unsigned v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
                                                  __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -157,22 +164,66 @@ __device__ __forceinline__ void conv_mainloop_x3(
   char* sbase = reinterpret_cast<char*>(smem);
 
 
+  // ---- The refill's addresses. Between two chunks of a tile every W and x address moves by a
+  // constant, so nothing below the chunk term is recomputed in the K loop: a thread keeps 32-bit
+  // byte offsets (computed here, once), the chunk term is a 64-bit pointer that is uniform over
+  // the workgroup and advances by a constant stride per chunk (scalar registers; the last chunk
+  // advances by 0 and so reloads itself). A 32-bit offset only spans what one chunk bounds
+  // (x3_offsets_fit: CK rows of x, one chunk's planes); cin * tin, the clip and the chunk live
+  // in the pointers.
   constexpr int WQ = X3W<KS, BM, PAIR, NT>::WQ, WTOT = X3W<KS, BM, PAIR, NT>::TOTAL;
+  // W: uint4 u = tid + r NT of the stage is (plane-octet g = u / BM, row = u % BM); its packed
+  // slot is g, or for the k7 pair chunks (7 real octets of 8 per packed plane) (g / 7) 8 + g % 7
+  auto w_slot = [](int g) {
+    if constexpr (PAIR && NOP != NO2P) return (g / NOP) * NO2P + g % NOP;
+    else return g;
+  };
+  // Tiles whose rows are whole waves (BM a multiple of 64): a wave's 64 uint4 of load r are 64
+  // consecutive rows of one slot, so slot * m_pad + row block is a per-wave scalar and the
+  // thread's part is its lane alone. Other tiles (32, 96 rows; contiguous slots): the loads'
+  // 32-row blocks repeat with period WP in r, NT * WP / BM slots further on: WP offset registers
+  // and a scalar step, plus one register for a last load that is clamped (WTOT % NT != 0).
+  constexpr bool WUNI = BM % 64 == 0;
+  static_assert(WUNI || (BM % 32 == 0 && NT % 32 == 0 && !(PAIR && NOP != NO2P)), "W offsets");
+  constexpr int WP = BM == 32 ? 1 : BM / 32;        // (NT / 32) * WP is a multiple of BM / 32
+  static_assert(WUNI || (NT * WP) % BM == 0, "W offsets: period");
+  constexpr bool WLAST = WTOT % NT != 0;            // the last load is clamped
+  constexpr int WNV = WUNI ? 1 : (WQ < WP ? WQ : WP) + 1;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const unsigned lane16 = (unsigned)lane * 16u;
+  unsigned wvo[WNV];
+  if constexpr (!WUNI) {
+    auto w_off = [&](int u) {
+      const int g = u / BM, row = u - g * BM;
+      return ((unsigned)g * (unsigned)a.m_pad + (unsigned)row) * 16u;
+    };
+#pragma unroll
+    for (int r = 0; r < WNV - 1; ++r) wvo[r] = w_off(tid + r * NT);
+    wvo[WNV - 1] = w_off(min(tid + (WQ - 1) * NT, WTOT - 1));  // clamped: no conditional load
+  }
+  const size_t wstride = (size_t)(PAIR ? 2 : 1) * 3 * NO2P * a.m_pad;  // uint4 per K-chunk
+  const u32x4* wc = w3 + (size_t)kc0 * wstride + m0;  // the chunk being loaded, this M tile
   u32x4 wr[WQ];
-  auto load_w = [&](int chunk) {
+  // x3_opaque: the offset registers pass through an empty asm inside the loop. Every load is
+  // then "uniform pointer + 32-bit register", the scalar-base form of global_load; left to
+  // itself the loop optimiser folds the offsets into the pointers and keeps one 64-bit
+  // induction variable in vector registers per load.
+  auto load_w = [&]() {
+    unsigned vo[WNV];
+#pragma unroll
+    for (int i = 0; i < WNV; ++i) vo[i] = x3_opaque(WUNI ? lane16 : wvo[i]);
 #pragma unroll
     for (int r = 0; r < WQ; ++r) {
-      const int u = min(tid + r * NT, WTOT - 1);  // clamped: no conditional load
-      if constexpr (PAIR) {
-        // stage entry ((half * 3 + plane) * NOP + po) * BM + row <- octet po of packed chunk
-        // 2 chunk + half
-        const int hp = u / (NOP * BM), r2 = u - hp * (NOP * BM);
-        const int po = r2 / BM, row = r2 - po * BM;
-        const int half = hp / 3, pl = hp - half * 3;
-        wr[r] = w3[(((size_t)(2 * chunk + half) * 3 + pl) * NO2P + po) * a.m_pad + m0 + row];
+      if constexpr (WUNI) {
+        const int un = min(wv + r * (NT / 64), WTOT / 64 - 1);  // clamped: no conditional load
+        const int g = (un * 64) / BM, rowb = un * 64 - g * BM;
+        const u32x4* ws = wc + ((unsigned)w_slot(g) * (unsigned)a.m_pad + (unsigned)rowb);
+        wr[r] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ws) + vo[0]);
+      } else if (WLAST && r == WQ - 1) {
+        wr[r] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wc) + vo[WNV - 1]);
       } else {
-        const int po = u / BM, row = u - po * BM;
-        wr[r] = w3[((size_t)chunk * 3 * NO2 + po) * a.m_pad + m0 + row];
+        const u32x4* ws = wc + (unsigned)((r / WP) * (NT * WP / BM)) * (unsigned)a.m_pad;
+        wr[r] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ws) + vo[r % WP]);
       }
     }
   };
@@ -183,6 +234,34 @@ __device__ __forceinline__ void conv_mainloop_x3(
       if (WTOT % NT == 0 || tid + r * NT < WTOT) ws[tid + r * NT] = wr[r];
   };
   float xr[XI][8];
+  // x: item e = tid + it NT is (channel octet c8, window position pos) in every chunk. Kept per
+  // item: the byte offset of (first channel of the octet, clamped time) within the chunk's CK
+  // rows, its slot in a stage plane (-1: no item) and whether the position is inside the input.
+  // The chunk's rows hang off one uniform pointer (row u of an octet: + u * tin, scalar).
+  // Phase-split view: view channel cv = c s + r of an octet is real channel c = cv >> psh at
+  // phase r = u & pmask (octets start at multiples of 8 and s divides 8), so the (cv >> psh)
+  // ptin product is scalar as well; the clamp of the phase's time index stays per element.
+  unsigned xvo[XI];
+  int xso[XI], xts[PH ? XI : 1];
+  bool xokp[XI];
+#pragma unroll
+  for (int it = 0; it < XI; ++it) {
+    const int e = tid + it * NT;
+    const int c8 = NC8 == 1 ? 0 : e / XW, pos = e - c8 * XW;
+    const int t = xbase + pos;
+    const int tc = min(max(t, 0), a.tin - 1);
+    const int c8v = e < nitems ? c8 : 0;
+    if constexpr (PH) {
+      xts[it] = (tc << psh) - ppad;
+      xvo[it] = (unsigned)(c8v * (8 >> psh)) * (unsigned)ptin * 4u;
+    } else {
+      xvo[it] = ((unsigned)(c8v * 8) * (unsigned)a.tin + (unsigned)tc) * 4u;
+    }
+    xso[it] = e < nitems ? c8 * XWP + pos : -1;
+    xokp[it] = t >= 0 && t < a.tin;
+  }
+  const size_t xstride = (size_t)(CK >> psh) * ptin;  // floats per K-chunk
+  const float* xc = xb + (size_t)kc0 * xstride;       // the chunk being loaded
   // Branch-free loads from clamped addresses, kept raw: the zeroing select outside the window
   // / input runs in store_x, after the MFMAs. (A select here makes the wave wait for the
   // load before the chunk's MFMAs, and vmcnt retires in order, so that wait also covers the
@@ -190,22 +269,46 @@ __device__ __forceinline__ void conv_mainloop_x3(
   // pair tiles: every input channel's Snake parameters in LDS behind the stage (their 16 per
   // chunk do not fit the scalar registers); the phase-split view: per real channel (cv >> psh)
   float* snl = reinterpret_cast<float*>(sbase + X3_STAGES * STG);  // after every stage
+  // ci0: the first channel of the chunk xc points to
   auto load_x = [&](int ci0) {
+    if (!PAIR && ci0 + CK > a.cin) {
+      // ragged last chunk (cin % CK != 0; pair chunks are whole): channels clamped per element
+#pragma unroll
+      for (int it = 0; it < XI; ++it) {
+        const int e = tid + it * NT;
+        const int c8 = NC8 == 1 ? 0 : e / XW, pos = e - c8 * XW;
+        const int tc = min(max(xbase + pos, 0), a.tin - 1);
+        const int cb = ci0 + (e < nitems ? c8 : 0) * 8;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int cv = min(cb + u, a.cin - 1);
+          if constexpr (PH) {
+            const int tp = min(max((tc << psh) + (cv & pmask) - ppad, 0), ptin - 1);
+            xr[it][u] = xb[(size_t)(cv >> psh) * ptin + tp];
+          } else {
+            xr[it][u] = xb[(size_t)cv * a.tin + tc];
+          }
+        }
+      }
+      return;
+    }
+    // (the view's per-element clamps and predicates stay in the loop: hoisted, they would take
+    // eight registers per item)
+    int ts[PH ? XI : 1];
+    unsigned vo[XI];
 #pragma unroll
     for (int it = 0; it < XI; ++it) {
-      const int e = tid + it * NT;
-      const int c8 = NC8 == 1 ? 0 : e / XW, pos = e - c8 * XW;
-      const int tc = min(max(xbase + pos, 0), a.tin - 1);
-      const int cb = ci0 + (e < nitems ? c8 : 0) * 8;
+      vo[it] = x3_opaque(xvo[it]);
+      if constexpr (PH) ts[it] = (int)x3_opaque((unsigned)xts[it]);
+    }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int cv = min(cb + u, a.cin - 1);
-        if constexpr (PH) {
-          const int tp = min(max((tc << psh) + (cv & pmask) - ppad, 0), ptin - 1);
-          xr[it][u] = xb[(size_t)(cv >> psh) * ptin + tp];
-        } else {
-          xr[it][u] = xb[(size_t)cv * a.tin + tc];
-        }
+    for (int u = 0; u < 8; ++u) {
+      const char* xu = reinterpret_cast<const char*>(xc + (size_t)(u >> psh) * ptin);
+#pragma unroll
+      for (int it = 0; it < XI; ++it) {
+        unsigned o = vo[it];
+        if constexpr (PH) o += (unsigned)min(max(ts[it] + (u & pmask), 0), ptin - 1) * 4u;
+        xr[it][u] = *reinterpret_cast<const float*>(xu + o);
       }
     }
   };
@@ -215,6 +318,7 @@ __device__ __forceinline__ void conv_mainloop_x3(
     // chunk outside the (divergent) item loop -- scalar loads, no vector-memory round trip
     // between the chunk's barriers -- and selected per item by its channel octet
     const bool sn = a.alpha != nullptr;
+    const bool ragged = !PAIR && ci0 + CK > a.cin;  // else every channel of the chunk is real
     constexpr int NU = NC8 == 1 ? 8 : 1;
     float alu[NU], iau[NU];
     if constexpr (NC8 == 1) {
@@ -229,20 +333,15 @@ __device__ __forceinline__ void conv_mainloop_x3(
     }
 #pragma unroll
     for (int it = 0; it < XI; ++it) {
-      const int e = tid + it * NT;
-      if (e >= nitems) continue;
-      const int c8 = NC8 == 1 ? 0 : e / XW, pos = e - c8 * XW;
-      const int t = xbase + pos;
-      const bool okp = t >= 0 && t < a.tin;
+      if (xso[it] < 0) continue;
+      const int c8 = NC8 == 1 ? 0 : (tid + it * NT) / XW;
+      const int ts = PH ? (int)x3_opaque((unsigned)xts[it]) : 0;  // as in load_x
       float v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int cv = ci0 + c8 * 8 + u;
-        bool ok = okp && cv < a.cin;
-        if constexpr (PH) {
-          const int tp = (t << psh) + (cv & pmask) - ppad;
-          ok = ok && tp >= 0 && tp < ptin;
-        }
+        bool ok = xokp[it];
+        if (ragged) ok = ok && ci0 + c8 * 8 + u < a.cin;
+        if constexpr (PH) ok = ok && (unsigned)(ts + (u & pmask)) < (unsigned)ptin;
         v[u] = ok ? xr[it][u] : 0.0f;
       }
       if (sn) {
@@ -267,9 +366,9 @@ __device__ __forceinline__ void conv_mainloop_x3(
       unsigned h[4], m[4], l[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) split3x2(v[2 * u], v[2 * u + 1], h[u], m[u], l[u]);
-      xs[(0 * NC8 + c8) * XWP + pos] = u32x4{h[0], h[1], h[2], h[3]};
-      xs[(1 * NC8 + c8) * XWP + pos] = u32x4{m[0], m[1], m[2], m[3]};
-      xs[(2 * NC8 + c8) * XWP + pos] = u32x4{l[0], l[1], l[2], l[3]};
+      xs[0 * NC8 * XWP + xso[it]] = u32x4{h[0], h[1], h[2], h[3]};
+      xs[1 * NC8 * XWP + xso[it]] = u32x4{m[0], m[1], m[2], m[3]};
+      xs[2 * NC8 * XWP + xso[it]] = u32x4{l[0], l[1], l[2], l[3]};
     }
   };
 
@@ -344,19 +443,22 @@ __device__ __forceinline__ void conv_mainloop_x3(
     }
   }
   int cur = 0;
-  load_w(kc0);
+  load_w();
   load_x(kc0 * CK);
   store_w(sbase);
   store_x(sbase, kc0 * CK);
   __syncthreads();
   for (int c = kc0; c < nchunks; ++c) {
     // Next chunk's loads in flight during this chunk's MFMAs. Unconditional (the last chunk
-    // reloads itself into the idle stage): under `if (more)` the compiler sinks the loads past
-    // the MFMAs into the store block, their only user.
+    // reloads itself into the idle stage: its pointers advance by 0, no branch around the
+    // loads): under `if (more)` the compiler sinks the loads past the MFMAs into the store
+    // block, their only user.
     const int cn = min(c + 1, nchunks - 1);
+    wc += c + 1 < nchunks ? wstride : 0;
+    xc += c + 1 < nchunks ? xstride : 0;
     char* nxt = sbase + (cur ^ (X3_STAGES - 1)) * STG;
     if constexpr (X3_STAGES == 2) {
-      load_w(cn);
+      load_w();
       load_x(cn * CK);
       __builtin_amdgcn_sched_barrier(0);
     } else if constexpr (XPF) {
@@ -373,7 +475,7 @@ __device__ __forceinline__ void conv_mainloop_x3(
       // from three workgroups per CU to two, the 128 x 128 one gains nothing.
       __syncthreads();  // every wave done with the stage
       if (c + 1 < nchunks) {
-        load_w(cn);
+        load_w();
         if constexpr (!XPF) load_x(cn * CK);
         // every load of the refill in flight before the first store waits on one (else the
         // x loads are issued only after the W stores: two memory round trips per chunk)
@@ -388,6 +490,13 @@ __device__ __forceinline__ void conv_mainloop_x3(
     __syncthreads();
     cur ^= X3_STAGES - 1;
   }
+}
+
+// The K loop's 32-bit byte offsets hold: at most 32 rows of x (one K-chunk's channels) and one
+// chunk's weight planes (at most 2 * 3 * 8 octet slots of m_pad rows, 16 bytes per row). The
+// entry points refuse anything longer (VRVQ_ERR_UNSUPPORTED).
+inline bool x3_offsets_fit(long long tin, long long m_pad) {
+  return 32 * tin * 4 <= 0x7fffffffLL && 49 * m_pad * 16 <= 0x7fffffffLL;
 }
 
 // LDS bytes the x3 mainloop needs for a window of XW positions.
