@@ -6,7 +6,7 @@ Groups
   plan      one case per distinct plan (entry kind, path, BM, BN, taps, x3 kind, split-K parts) of
             tests/golden/conv_plan_parent.json plus the five plans only the direct kernel tests of
             tests/test_gpu_parity.py reach (EXTRA_PLANS). The fixture gives the plan keys only:
-            every shape comes from the dispatch rules of csrc/conv.hip restated in plan_shape(),
+            every shape comes from the planner's rules (csrc/conv_plan.h) restated in plan_shape(),
             the smallest that still has B >= 2, three K chunks with a ragged last one, a ragged
             last N tile, tout % 4 != 0 and a ragged last M tile wherever the plan admits them.
   epilogue  two cases per distinct epilogue (kind, BM, BN): tout % 4 == 0 with a residual, tanh
@@ -102,7 +102,7 @@ def chunk_channels(KS, BM, BN, x3):
     return ck0 // 2 if BM > 128 and ck0 >= 8 else ck0
 
 
-# GEMM columns that give a tile width with a ragged last tile of two or more (tile_width():
+# GEMM columns that give a tile width with a ragged last tile of two or more (conv_plan.h tile_width():
 # <= 32 -> 32; <= 96 -> 32, or 96 at 384 workgroups / for the x3 ConvTranspose; above, 64 where
 # that pads under 0.7 of what 128 pads), and the same with tout % 4 == 0.
 COLUMNS = {32: 70, 96: 87, 64: 130, 128: 197, 256: 641}
@@ -112,7 +112,7 @@ K7_DILATIONS = (1, 3, 9)
 
 def plan_shape(key, aligned=False, n=0):
     """A case's shape arguments for a plan key (kind, path, BM, BN, KS, x3, S) by the rules of
-    dispatch_tiles() / tile_width() / splitk_parts(); n varies what the plan leaves free (the
+    choose_tile() / tile_width() / splitk_parts() of csrc/conv_plan.h; n varies what the plan leaves free (the
     k7 dilation, the ConvTranspose's stride). aligned: tout % 4 == 0."""
     kind, path, BM, BN, KS, x3, S = key
     assert path == 0

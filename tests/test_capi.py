@@ -94,7 +94,7 @@ def test_argument_errors_raise_before_launch():
     # producer-side snake without its alpha
     assert lib.vrvq_conv1d(p, 1, 4, 100, None, None, p, None, 4, 128, 7, 1, 3, 1, None, None,
                            0, None, 100, None, None, p, None) == 10001
-    # split-K workspace of the deep-K T <= 96 layers (conv.hip splitk_parts): S parts x B x
+    # split-K workspace of the deep-K T <= 96 layers (conv_plan.h splitk_parts): S parts x B x
     # M / 128 tiles x 128 x 96 fp32, S = 4 capped at chunks / 8 -- a function of the layer,
     # not of the batch
     def ws(*shape):

@@ -6,7 +6,9 @@ PROJ_TILE_CASES of test_gpu_rvq_part.py and the edges of every tile rule. Each r
 arguments, its status, `launch` = [BM, BN, KS, x3, S] (null: no MFMA tile ran, the record before
 the call was still there afterwards) and `ws_need` = vrvq_conv1d_workspace's bytes.
 
-A change of a tile rule shows here, without a GPU, as the rows whose kernel it moves."""
+The planner is csrc/conv_plan.h (plan_conv1d / plan_conv_transpose1d); vrvq_conv_plan also looks
+the plan's kernel up in the launch tables of csrc/conv_k*.hip. A change of a tile rule shows here,
+without a GPU, as the rows whose kernel it moves."""
 import ctypes
 import json
 import os

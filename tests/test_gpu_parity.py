@@ -346,7 +346,7 @@ def test_conv1d_x3_vs_torch(case):
 def test_conv1d_x3_long_rows_vs_torch(case):
     """x3 convs over long rows, as vrvq_conv_plan places them: the three k7 cases (rows of >= 640
     samples, >= 128 output channels, Cin % 16 == 0) run the pair-chunk 64 x 256 tiles of
-    conv_x3.h (dispatch_tiles takes them only for such Cin; launch_cfg runs a pair tile on plain
+    conv_x3.h (choose_tile takes them only for such Cin; plan_mfma runs a pair tile on plain
     chunks for any other), the k1 + skip GEMMs run 192 x 64, 128 x 64 and 128 x 128 tiles on
     plain 32-channel chunks; every case ends in a ragged last tile."""
     test_conv1d_x3_vs_torch(case)
@@ -386,7 +386,7 @@ def test_conv1d_strided_x3_vs_torch(case):
     assert rel_err(ys.cpu().numpy(), _snake_ref(y3, a_next).cpu().numpy()) < 1e-6
 
 
-# The split-K T <= 96 layers (conv.hip splitk_parts: 128 x 96 tiles, the K chunks cut into parts
+# The split-K T <= 96 layers (conv_plan.h splitk_parts: 128 x 96 tiles, the K chunks cut into parts
 # whose sums the workspace holds): (B, cin, cout, tin, k, stride, pad, dil, snake, residual, epi)
 SPLITK_CASES = [(3, 512, 1024, 696, 16, 8, 4, 1, True, False, 0),   # EncoderBlock 512 -> 1024 s8
                 (3, 1024, 1024, 87, 3, 1, 1, 1, True, False, 0),    # ImportanceSubnet in_block
@@ -610,7 +610,7 @@ def test_batch_invariance_full_batch(manifest):
     (the oracle checks 8 of the 32 clips): every output bit-identical, so no clip position of
     the full batch is computed differently from the small-batch path the oracle pins. (Tile
     widths that change a layer's K order -- the 2-tap x3 GEMMs' 32-wide pair tile vs the
-    96-wide one -- are fixed per layer, not chosen by batch: conv.hip dispatch_tiles.)"""
+    96-wide one -- are fixed per layer, not chosen by batch: conv_plan.h tile_width.)"""
     model = model_for(manifest, "golden_nq8")
     audio = t(synthetic_audio(32, 44100, seed=2024))
     with torch.no_grad():

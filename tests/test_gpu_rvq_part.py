@@ -430,7 +430,7 @@ def test_rvq_stress_fixtures_on_default_path(manifest, name):
 
 
 # ------------------------------------------------------------------ projection epilogue, every tile
-# name, cin, B, T, mode, the launch {BM, BN, KS, x3, S} (conv.hip tile_width / dispatch_tiles:
+# name, cin, B, T, mode, the launch {BM, BN, KS, x3, S} (conv_plan.h tile_width / choose_tile:
 # T <= 96 runs 32-wide tiles, 96-wide from 384 workgroups = B 48; T = 130 64-wide, T = 97
 # 128-wide; k3 runs plain x3 chunks; Cin = 128 has too few K chunks to split, the deep layer
 # splits in 4 when it has a workspace). mode: "op" the torch op (always offers the workspace),

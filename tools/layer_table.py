@@ -132,7 +132,7 @@ def main():
     conv = []
     for r in rows:
         if "conv_splitk_epilogue_kernel" in r["Kernel_Name"] and conv:
-            # a split-K layer (conv.hip launch_splitk): its K parts and their epilogue launch,
+            # a split-K layer (conv_plan.h splitk_parts): its K parts and their epilogue launch,
             # stream-ordered, timed as one layer from the first start to the epilogue's end
             conv[-1] = dict(conv[-1], End_Timestamp=r["End_Timestamp"])
         elif any(k in r["Kernel_Name"] for k in ("conv_mfma_kernel", "conv_small", "conv_cout1",

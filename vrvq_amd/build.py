@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import glob
 import os
+from concurrent.futures import ThreadPoolExecutor
 import shutil
 import subprocess
 import sys
@@ -25,6 +26,7 @@ ARCH = os.environ.get("VRVQ_OFFLOAD_ARCH", "gfx950")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize",
          f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 OBJ_DIR = os.path.join(HERE, "build")
+MAX_COMPILERS = 16  # hipcc processes at once
 
 
 def sources():
@@ -55,9 +57,9 @@ def hipcc() -> str:
 
 
 def _compile_and_link(out: str, extra, verbose: bool, tag: str, srcs=None) -> str:
-    """One hipcc process per translation unit (they compile in parallel), then one link."""
+    """One hipcc process per translation unit (at most MAX_COMPILERS at once), then one link."""
     os.makedirs(OBJ_DIR, exist_ok=True)
-    procs, objs = [], []
+    cmds, objs = [], []
     headers = [d for d in deps() if not d.endswith(".hip")]
     for src in (srcs or sources()):
         obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + tag + ".o")
@@ -69,8 +71,10 @@ def _compile_and_link(out: str, extra, verbose: bool, tag: str, srcs=None) -> st
                                                  "-o", obj]
         if verbose:
             print("[vrvq_amd] " + " ".join(cmd), file=sys.stderr)
-        procs.append((subprocess.Popen(cmd), cmd))
-    failed = [cmd for p, cmd in procs if p.wait() != 0]
+        cmds.append(cmd)
+    with ThreadPoolExecutor(MAX_COMPILERS) as pool:
+        codes = list(pool.map(subprocess.call, cmds))
+    failed = [cmd for code, cmd in zip(codes, cmds) if code != 0]
     if failed:
         raise subprocess.CalledProcessError(1, failed[0])
     tmp = out + ".tmp"

@@ -3,6 +3,7 @@
 // LDS-transposed epilogue. See conv.hip for the GEMM mapping and the MFMA operand layouts.
 #pragma once
 #include "common.h"
+#include "conv_geom.h"
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -51,8 +52,8 @@ struct ConvArgs {
   float* ks_part;
 };
 
-// v = h + m + l exactly (RNE at each step; conv_x3.h split3x2), two values per call
-__device__ __forceinline__ void split3x2_core(float v0, float v1, unsigned& h, unsigned& m,
+// Three bf16 planes of two floats (RNE at each step): v = h + m + l exactly (conv_x3.h).
+__device__ __forceinline__ void split3x2(float v0, float v1, unsigned& h, unsigned& m,
                                               unsigned& l) {
   typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
   typedef float f32x2_ __attribute__((ext_vector_type(2)));
@@ -68,18 +69,10 @@ __device__ __forceinline__ void split3x2_core(float v0, float v1, unsigned& h, u
   l = __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf16x2_));
 }
 
+// Input channels per K-chunk of the fp32-input loop (conv_geom.h chunk_ck).
 template <int KS, int BM, int BN>
 struct ChunkCfg {
-  // Input channels per K-chunk: CK*KS ~ 32..64 rows of W per stage (half for 192-row tiles,
-  // so two double-buffered stages still fit twice per CU).
-  // The strided encoder convs (KS = 2 s in {4, 8, 16}) take half of that: with their wide
-  // input windows a full chunk needs ~99 KB for the two stages, one workgroup per CU, and
-  // their short K then leaves every prologue / epilogue exposed (measured at B = 32:
-  // 64->128 s2 877 -> 680 us, 128->256 s4 1279 -> 1072, 512->1024 s8 at BN 32 888 -> 696;
-  // but 256->512 s8 at BN 128 1319 -> 1606, so k16 keeps 4 channels on 128-wide tiles).
-  static constexpr int CK0 = KS == 1 ? 32 : KS <= 3 ? 16 : KS == 4 ? 8 : KS == 7 ? 8
-                             : KS == 8 ? 4 : BN > 32 ? 4 : 2;
-  static constexpr int CK = (BM > 128 && CK0 >= 8) ? CK0 / 2 : CK0;
+  static constexpr int CK = chunk_ck(KS, BM, BN);
 };
 
 __device__ __forceinline__ float apply_epi(float v, int epi) {
@@ -88,26 +81,22 @@ __device__ __forceinline__ float apply_epi(float v, int epi) {
   return v;
 }
 
-// Largest input window a thread stages per K-chunk: stride <= KS/2 for the strided (k = 2s)
-// encoder convs, dilation <= 9 for the k = 7 residual-unit convs.
+// Largest input window a thread stages per K-chunk (conv_geom.h win_xw_max).
 template <int KS, int BN>
 struct WinCfg {
-  static constexpr int SMAX = (KS == 4 || KS == 8 || KS == 16) ? KS / 2 : 1;
-  static constexpr int DMAX = KS == 7 ? 9 : 1;
-  static constexpr int XW_MAX = (BN - 1) * SMAX + (KS - 1) * DMAX + 1;
-  static constexpr int PER_ROW = (XW_MAX + 63) / 64;  // positions per lane per row
+  static constexpr int SMAX = win_smax(KS);
+  static constexpr int DMAX = win_dmax(KS);
+  static constexpr int XW_MAX = win_xw_max(KS, BN);
+  static constexpr int PER_ROW = win_per_row(KS, BN);  // positions per lane per row
 };
 
-// Epilogue column passes: the accumulator tile goes through LDS in BM x (BN / EPASS) pieces of
-// at most 64 KiB, EPASS dividing the wave-column count.
+// Epilogue column passes (conv_geom.h epi_passes).
 template <int BM, int BN, int WN>
 struct EpiCfg {
-  static constexpr int need = (BM * BN * 4 + 65535) / 65536;
-  static constexpr int EPASS = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
+  static constexpr int EPASS = epi_passes(BM, BN);
   static_assert(WN % EPASS == 0 || EPASS == 1, "epilogue passes must split the wave columns");
-  static constexpr int BNP = BN / EPASS;
+  static constexpr int BNP = epi_bnp(BM, BN);
 };
-
 
 // Tile geometry shared by the mainloop / epilogue of one <BM, BN, WM, NW> configuration.
 template <int BM, int BN, int WM, int NW>
@@ -304,12 +293,7 @@ __device__ __forceinline__ void conv_mainloop(
 // does not change a bit). The chain then sums the eight splits in order, as the three-launch
 // path does: the quantizer's input never goes back to HBM as z and is not re-read from it.
 // z crosses LDS as three planes [plane][frame][channel] (rows of 128 + 8 channels: conflict-free
-// 16-B B reads), 32 frames per pass.
-constexpr int PJE_LDB = 136;                      // bf16 per frame row
-constexpr int PJE_FR = 32;                        // frames per pass
-constexpr int PJE_PLANE = PJE_FR * PJE_LDB * 2;   // bytes per plane (8,704)
-constexpr int PJE_LDS = 3 * PJE_PLANE;            // 26,112 B
-
+// 16-B B reads), 32 frames per pass (conv_geom.h PJE_*).
 template <int BM, int BN, int WM, int NW>
 __device__ __forceinline__ void proj_epilogue(
     const ConvArgs& a, float* smem,
@@ -361,8 +345,8 @@ __device__ __forceinline__ void proj_epilogue(
           for (int u = 0; u < 4; ++u)
             v[u] = a.bias ? acc[i][j][4 * q + u] + a.bias[m0 + ml + u] : acc[i][j][4 * q + u];
           unsigned h[2], mm[2], l[2];
-          split3x2_core(v[0], v[1], h[0], mm[0], l[0]);
-          split3x2_core(v[2], v[3], h[1], mm[1], l[1]);
+          split3x2(v[0], v[1], h[0], mm[0], l[0]);
+          split3x2(v[2], v[3], h[1], mm[1], l[1]);
           char* d = lds + lr * (PJE_LDB * 2) + ml * 2;
           *reinterpret_cast<uint2*>(d) = make_uint2(h[0], h[1]);
           *reinterpret_cast<uint2*>(d + PJE_PLANE) = make_uint2(mm[0], mm[1]);

@@ -30,61 +30,21 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace vrvq_conv {
 
-// LDS stages of the x3 K loop. 1 (default): one stage, refilled between two barriers after
-// the chunk's MFMAs; half the LDS and no prefetch registers let two workgroups share a CU,
-// and each one's MFMAs cover the other's loads, barriers and epilogue. 2: double-buffered
-// with the next chunk prefetched into registers during the MFMAs, one workgroup per CU for
-// the larger tiles.
-// Tiles up to 128 x 128 take 1 (two workgroups per CU), the 192-row x 128 tiles 2 (their
-// registers allow one wave per SIMD, so the prefetch has to hide the loads).
+// Stage count, pair chunks and K-chunk shape: conv_geom.h, where the measurements behind them stand.
 template <int BM, int BN>
-constexpr int x3_stages() { return BM * BN <= 128 * 128 ? 1 : 2; }
+constexpr int x3_stages() { return x3_stages(BM, BN); }
 
-// 64 x 256 k7 tiles ("pair" chunks): a K-chunk of 16 channels, two channel octets per tap, so
-// the 7 taps fill 14 octet slots = 7 MFMA steps with no zero octet (an 8-channel k7 chunk pads
-// its 7 octets to 8: 1/8 of its MFMAs multiply zero weights), 168 MFMAs per wave between two
-// barriers instead of 96. The weight planes stay in the 8-channel packing (two packed chunks
-// per K-chunk, pad octets skipped while staging): 43 KB W + <= 30 KB x per stage, two
-// workgroups per CU.
-// A pair tile needs Cin to be a multiple of the K-chunk (launch_cfg falls back otherwise). The
-// k1 + skip GEMMs on the same construction (128 x 64 tiles, two 32-channel packed chunks per
-// K-chunk) measured slower: profiles/r03_x3_pair_ab.txt.
-// The same pairing for the 2-tap GEMMs (the strided encoder convs through the phase-split view
-// and the polyphase ConvTranspose): 32-channel K-chunks of 8 octets = 4 MFMA steps (the
-// 16-channel chunk has 2), on the 128- and 32-wide tiles up to 128 rows (one LDS stage, two
-// workgroups per CU). Measured per layer at B = 32 (profiles/r04d_layer_table.txt vs
-// r03f_layer_table.txt): 128 x 128 tiles 5-13 % faster (64->128 s2, 128->256 s4, ConvT 384->192
-// s4), 128 x 32 10 % (512->1024 s8 at T = 87); 128 x 64 and 128 x 96 4-14 % slower (the doubled
-// weight stage costs the 128 x 64 tile its third workgroup per CU): those keep 16-channel chunks.
 template <int KS, int BM, int BN>
-constexpr bool x3_pair() {
-  return (KS == 7 && BM == 64 && BN == 256) ||
-         (KS == 2 && BM <= 128 && (BN == 128 || BN == 32));
-}
+constexpr bool x3_pair() { return x3_pair(KS, BM, BN); }
 
 template <int KS, bool PAIR = false>
 struct X3Cfg {  // PAIR = false: also the HBM packing of the weight planes (vrvq_pack_x3_weight)
-  static constexpr int CK = (PAIR ? 2 : 1) * (KS == 1 ? 32 : KS <= 3 ? 16 : 8);  // channels per K-chunk
-  static constexpr int NC8 = CK / 8;                        // channel octets per tap
-  static constexpr int NO = KS * NC8;                       // octets per chunk
-  static constexpr int NO2 = (NO + 1) & ~1;                 // padded to MFMA steps
-  static constexpr int NSTEP = NO2 / 2;
+  static constexpr int CK = x3_ck(KS, PAIR);        // channels per K-chunk
+  static constexpr int NC8 = x3_nc8(KS, PAIR);      // channel octets per tap
+  static constexpr int NO = x3_no(KS, PAIR);        // octets per chunk
+  static constexpr int NO2 = x3_no2(KS, PAIR);      // padded to MFMA steps
+  static constexpr int NSTEP = x3_nstep(KS, PAIR);
 };
-
-// Three planes of two floats (RNE at each step): v = h + m + l exactly.
-__device__ __forceinline__ void split3x2(float v0, float v1, unsigned& h, unsigned& m,
-                                         unsigned& l) {
-  const f32x2 v = {v0, v1};
-  const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  const f32x2 hf = {__uint_as_float(hu << 16), __uint_as_float(hu & 0xffff0000u)};
-  const f32x2 r = v - hf;
-  const unsigned mu = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-  const f32x2 mf = {__uint_as_float(mu << 16), __uint_as_float(mu & 0xffff0000u)};
-  const f32x2 s = r - mf;
-  h = hu;
-  m = mu;
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf16x2));
-}
 
 // A value the optimiser cannot see through: keeps what is derived from it where it is written
 // (conv_mainloop_x3's refill offsets). No instruction.
@@ -98,12 +58,9 @@ __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
                                                  __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-// LDS bytes of one pipeline stage.
+// LDS bytes of the W planes of one pipeline stage.
 template <int KS, int BM, bool PAIR>
-__host__ __device__ constexpr int x3_stage_w_bytes() {
-  return PAIR ? 2 * 3 * X3Cfg<KS>::NO * BM * 16 : 3 * X3Cfg<KS>::NO2 * BM * 16;
-}
-__host__ __device__ inline int x3_xwp(int xw) { return (xw + 3) & ~3; }
+constexpr int x3_stage_w_bytes() { return x3_stage_w_bytes(KS, BM, PAIR); }
 
 // W chunk staging through registers: uint4 u = tid + r*NT of the stage holds
 // (plane, octet, row) = (u / BM) -> w3[((chunk*3 + plane)*NO2 + octet)*m_pad + m0 + row].
@@ -142,7 +99,7 @@ __device__ __forceinline__ void conv_mainloop_x3(
   static_assert(!PAIR || X3Cfg<KS, true>::NSTEP == NOP, "pair step q = packed octet q");
   constexpr int NT = TC::NT, RM = TC::RM, RN = TC::RN, TM = TC::TM, TN = TC::TN;
   constexpr int CK = XC::CK, NC8 = XC::NC8, NO = XC::NO, NO2 = XC::NO2, NSTEP = XC::NSTEP;
-  constexpr int XW_MAX = (BN - 1) + (KS - 1) * (KS == 7 ? 9 : 1) + 1;
+  constexpr int XW_MAX = x3_xw_max(KS, BN);
   constexpr int XI = (NC8 * XW_MAX + NT - 1) / NT;  // x items (octet, position) per thread
   constexpr int WB = x3_stage_w_bytes<KS, BM, PAIR>();
 
@@ -492,19 +449,10 @@ __device__ __forceinline__ void conv_mainloop_x3(
   }
 }
 
-// The K loop's 32-bit byte offsets hold: at most 32 rows of x (one K-chunk's channels) and one
-// chunk's weight planes (at most 2 * 3 * 8 octet slots of m_pad rows, 16 bytes per row). The
-// entry points refuse anything longer (VRVQ_ERR_UNSUPPORTED).
-inline bool x3_offsets_fit(long long tin, long long m_pad) {
-  return 32 * tin * 4 <= 0x7fffffffLL && 49 * m_pad * 16 <= 0x7fffffffLL;
-}
-
 // LDS bytes the x3 mainloop needs for a window of XW positions.
 template <int KS, int BM, int BN, bool PAIR = x3_pair<KS, BM, BN>()>
 inline size_t x3_lds_bytes(int xw, int cin) {
-  const size_t xb = 3 * (size_t)X3Cfg<KS, PAIR>::NC8 * x3_xwp(xw) * 16;
-  const size_t snake = PAIR ? 2 * (size_t)cin * sizeof(float) : 0;
-  return x3_stages<BM, BN>() * ((size_t)x3_stage_w_bytes<KS, BM, PAIR>() + xb) + snake;
+  return (size_t)x3_lds_bytes(KS, BM, BN, PAIR, xw, cin);
 }
 
 }  // namespace vrvq_conv
