@@ -467,7 +467,38 @@ int vrvq_bpf(const float* mask, const float* bits, int batch, int nq, int frames
  *                        elements is held in registers, a larger one is re-read per iteration.
  *   vrvq_scale_imp_rows  out[b][t] = imp[b][t] * levels[b] (one rounding). The RVQ entry points
  *                        given this map and level = 1.0f (an exact product) compute the
- *                        expression above for each row's own level, bit for bit. */
+ *                        expression above for each row's own level, bit for bit.
+ *
+ * Capped rate control (library version 111): a cap on the rate of every packet next to the
+ * group's budget. A packet is a run of P = packet_frames consecutive frames of one row; a row has
+ * NP = ceil(T / P) packets, packet p covers frames [p P, min((p + 1) P, T)) (the last may be
+ * short, P >= T is one packet per row). bits_bp(l) is the int64 total of packet (b, p) at level l.
+ *   vrvq_rate_solve_capped  bits, group_off, budget, level_lo, level_hi as for vrvq_rate_solve;
+ *                        packet_budget [NP] (int64, device): the bits packet p of any row may take.
+ *                        cap[b][p] = the largest fp32 level in [level_lo, level_hi] with
+ *                        bits_bp(cap) <= packet_budget[p], what vrvq_rate_solve gives for that
+ *                        packet alone (level_lo if even level_lo exceeds it: the packet is
+ *                        infeasible; level_hi if level_hi fits). lambda[g] = the largest fp32
+ *                        level in [level_lo, level_hi] with
+ *                        sum over (b, p) in g of bits_bp(min(lambda, cap[b][p])) <= budget[g]: the
+ *                        sum does not decrease with lambda for imp >= 0, so the same bisection is
+ *                        exact (<= 31 passes, bounded by the interval and not by the data).
+ *                        level_out[g] = lambda[g], total_out[g] the sum at it, status[g] as for
+ *                        vrvq_rate_solve (1: over budget with every packet at level_lo; 2: level_hi
+ *                        fits, the caps included). packet_level [B][NP] = min(lambda[g], cap),
+ *                        packet_total [B][NP] (int64) the packet's bits at it, packet_status
+ *                        [B][NP]: 0 the packet runs at its group's level, 1 infeasible (it runs at
+ *                        level_lo and exceeds packet_budget[p]), 2 limited by its cap (cap <
+ *                        lambda). A row of no valid group keeps packet_level = cap, the total at
+ *                        it and packet_status 1 or 2. Groups should not share rows (the shared
+ *                        rows' packet outputs are those of one of the groups). Two launches, no
+ *                        host sync, no atomics: one wave per packet for the caps (a packet of up to
+ *                        256 frames in registers, a longer one re-read per pass), then one
+ *                        256-thread workgroup per group (up to 4096 elements and their caps in
+ *                        registers, a larger group re-read per pass) and one wave per packet of
+ *                        the group for the packet outputs.
+ *   vrvq_scale_imp_packets  out[b][t] = imp[b][t] * packet_level[b][t / P] (one rounding): with
+ *                        level = 1.0f the RVQ entry points run every packet at its own level. */
 int vrvq_rate_curve(const float* imp, int batch, int frames, int nq, const int* bits,
                     const float* levels, int n_levels, long long* total_bits,
                     vrvq_stream_t stream);
@@ -477,6 +508,14 @@ int vrvq_rate_solve(const float* imp, int batch, int frames, int nq, const int* 
                     vrvq_stream_t stream);
 int vrvq_scale_imp_rows(const float* imp, int batch, int frames, const float* levels, float* out,
                         vrvq_stream_t stream);
+int vrvq_rate_solve_capped(const float* imp, int batch, int frames, int nq, const int* bits,
+                           const int* group_off, int n_groups, const long long* budget,
+                           const long long* packet_budget, int packet_frames, float level_lo,
+                           float level_hi, float* level_out, long long* total_out, int* status,
+                           float* packet_level, long long* packet_total, int* packet_status,
+                           vrvq_stream_t stream);
+int vrvq_scale_imp_packets(const float* imp, int batch, int frames, const float* packet_level,
+                           int packet_frames, float* out, vrvq_stream_t stream);
 
 /* Distortion metrics (models/utils.py:91-129 cal_metrics: torchmetrics' SI-SDR / SI-SNR / SNR
  * formulas for fp32 input, and the L1 distance), per row and without a host sync.

@@ -64,6 +64,9 @@ SIGNATURES = {
     "vrvq_rate_curve": [_P, _I, _I, _I, _P, _P, _I, _P, _P],
     "vrvq_rate_solve": [_P, _I, _I, _I, _P, _P, _I, _P, _F, _F, _P, _P, _P, _P],
     "vrvq_scale_imp_rows": [_P, _I, _I, _P, _P, _P],
+    "vrvq_rate_solve_capped": [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P,
+                               _P, _P],
+    "vrvq_scale_imp_packets": [_P, _I, _I, _P, _I, _P, _P],
     "vrvq_signal_metrics_workspace": [_I, ctypes.c_longlong, _P],
     "vrvq_signal_metrics": [_P, _P, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, ctypes.c_longlong,
                             _P],

@@ -220,7 +220,8 @@ def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
              verbose: bool = False, normalize_db: Optional[float] = -16,
              n_quantizers: Optional[int] = None, level: float = 1.0, max_batch: int = 64,
              sample_rate: Optional[int] = None, target_kbps: Optional[float] = None,
-             container: str = "dac") -> Union[DACFile, VRVQFile]:
+             container: str = "dac", max_kbps: Optional[float] = None,
+             packet_frames: Optional[int] = None) -> Union[DACFile, VRVQFile]:
     """models/dac_base.py:162-240 on the HIP encode path (see the module docstring).
 
     `container`: "dac" (a DACFile) or "vrvq" (a VRVQFile: the same codes, bit-packed on the
@@ -232,9 +233,18 @@ def compress(model, audio_path_or_signal, win_duration: Optional[float] = 1.0,
     together stay within target_kbps over their frames -- is solved on the device from their
     importance maps (utils.solve_levels, pooled), so bits move between windows. Codes do not
     depend on the level: only the masks are built from it, there is no second encode, and the
-    file equals compress(level=solve_file_level(...))."""
+    file equals compress(level=solve_file_level(...)).
+
+    `max_kbps` (with target_kbps) caps the short-term rate as well: no packet of `packet_frames`
+    consecutive frames of a window exceeds max_kbps (packets restart at every window; None: one
+    packet per window, so no window of the file exceeds max_kbps), while the file still meets
+    target_kbps (utils.solve_levels_capped, pooled: the levels then vary from packet to packet,
+    and the bits a capped packet gives up go to the others). With "vrvq" the count field is
+    budgeted in both constraints. A max_kbps some packet exceeds even at level_min raises
+    ValueError."""
     return _compress(model, audio_path_or_signal, False, win_duration, verbose, normalize_db,
-                     n_quantizers, level, max_batch, sample_rate, target_kbps, container)
+                     n_quantizers, level, max_batch, sample_rate, target_kbps, container,
+                     max_kbps, packet_frames)
 
 
 def solve_file_level(model, audio, target_kbps: float, **compress_kw) -> float:
@@ -246,11 +256,18 @@ def solve_file_level(model, audio, target_kbps: float, **compress_kw) -> float:
 @torch.no_grad()
 def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose=False,
               normalize_db=-16, n_quantizers=None, level=1.0, max_batch=64, sample_rate=None,
-              target_kbps=None, container="dac"):
+              target_kbps=None, container="dac", max_kbps=None, packet_frames=None):
     if container not in ("dac", "vrvq"):
         raise ValueError(f"compress: container must be 'dac' or 'vrvq', not {container!r}")
     packed = container == "vrvq"
     vbr = getattr(model, "model_type", "CBR") == "VBR"
+    if max_kbps is not None and target_kbps is None:
+        raise ValueError("compress: max_kbps needs target_kbps")
+    if packet_frames is not None and (max_kbps is None or packet_frames != int(packet_frames)
+                                      or packet_frames < 1):
+        raise ValueError("compress: packet_frames is an integer >= 1 and needs max_kbps")
+    if max_kbps is not None and level_only:
+        raise ValueError("solve_file_level: a capped file has no single level")
     if target_kbps is not None:
         if not vbr:
             raise ValueError("compress: target_kbps needs a VBR model (this one is CBR)")
@@ -328,18 +345,40 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
             from . import utils
             imp = torch.cat(imps, 0)
             nq = model.n_codebooks
-            lv, _, status = utils.solve_levels(
-                imp, target_kbps, nq=nq, sample_rate=model.sample_rate,
-                hop_length=model.hop_length, level_min=model.quantizer.level_min,
-                level_max=model.quantizer.level_max, pooled=True,
-                side_bits_per_frame=count_bits_of(nq) if packed else 0)
+            side = count_bits_of(nq) if packed else 0
+            kw = dict(nq=nq, sample_rate=model.sample_rate, hop_length=model.hop_length,
+                      level_min=model.quantizer.level_min, level_max=model.quantizer.level_max,
+                      pooled=True, side_bits_per_frame=side)
+            if max_kbps is not None:
+                # packets live inside each window; one per window unless packet_frames says so
+                P = imp.shape[-1] if packet_frames is None else int(packet_frames)
+                r = utils.solve_levels_capped(imp, target_kbps, max_kbps, P, **kw)
+                lv, status = r["level"], r["status"]
+                bad = (r["packet_status"] == 1).cpu().numpy()           # the host sync
+                if bad.any():
+                    T = imp.shape[-1]
+                    n_f = np.minimum(P, T - P * np.arange(bad.shape[1]))[None]
+                    kbps = (r["packet_bits"].cpu().numpy() + side * n_f) / n_f \
+                        * (model.sample_rate // model.hop_length) / 1000.0
+                    raise ValueError(
+                        f"compress: max_kbps = {max_kbps} is below the rate of {int(bad.sum())} "
+                        f"packet(s) of {P} frames at level_min = {model.quantizer.level_min} "
+                        f"(up to {float(kbps[bad].max()):.3f} kbps)")
+            else:
+                lv, _, status = utils.solve_levels(imp, target_kbps, **kw)
             if int(status.item()) == 1:
                 raise ValueError(f"compress: {target_kbps} kbps is below the file's rate at "
                                  f"level_min = {model.quantizer.level_min}")
             file_level = float(lv.item())
             if level_only:
                 return file_level
-            mask = utils.generate_mask_hard(utils.scale_importance(imp, file_level, float(nq)), nq)
+            if max_kbps is not None:  # every packet's own level in the map, level 1.0 after it
+                from . import ops
+                rows = ops.scale_imp_packets(imp, r["packet_level"], P)
+                mask = utils.generate_mask_hard(utils.scale_importance(rows, 1.0, float(nq)), nq)
+            else:
+                mask = utils.generate_mask_hard(
+                    utils.scale_importance(imp, file_level, float(nq)), nq)
             if not packed:
                 codes = codes.masked_fill(mask == 0, model.codebook_size)
         elif level_only:
@@ -358,7 +397,9 @@ def _compress(model, audio_path_or_signal, level_only, win_duration=1.0, verbose
                             channels=nac, sample_rate=original_sr, padding=model.padding,
                             level=file_level if target_kbps is not None else
                             (float(level) if mask is not None else None),
-                            target_kbps=None if target_kbps is None else float(target_kbps))
+                            target_kbps=None if target_kbps is None else float(target_kbps),
+                            max_kbps=None if max_kbps is None else float(max_kbps),
+                            packet_frames=None if max_kbps is None else P)
         dac = DACFile(codes=codes.cpu(), chunk_length=chunk_length,
                       original_length=original_length, input_db=input_db.cpu(), channels=nac,
                       sample_rate=original_sr, padding=model.padding,

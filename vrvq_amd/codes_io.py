@@ -394,12 +394,19 @@ class VRVQFile:
     padding: bool
     level: Optional[float] = None
     target_kbps: Optional[float] = None
+    max_kbps: Optional[float] = None       # compress(max_kbps=...): the cap of every packet of
+    packet_frames: Optional[int] = None    # packet_frames frames; in the header only when set
 
     def _header(self) -> dict:
         bs = self.bitstream
         input_db = self.input_db
         if isinstance(input_db, torch.Tensor):
             input_db = input_db.detach().cpu().numpy()
+        # a file written without a cap has the header, byte for byte, it had before caps existed
+        capped = {k: v for k, v in (
+            ("max_kbps", None if self.max_kbps is None else float(self.max_kbps)),
+            ("packet_frames", None if self.packet_frames is None else int(self.packet_frames)))
+            if v is not None}
         return {
             "format": "VRVQ bitstream", "version": BITSTREAM_VERSION,
             "n_codebooks": bs.n_codebooks, "codebook_size": bs.codebook_size,
@@ -411,6 +418,7 @@ class VRVQFile:
             "padding": bool(self.padding),
             "level": None if self.level is None else float(self.level),
             "target_kbps": None if self.target_kbps is None else float(self.target_kbps),
+            **capped,
         }
 
     def save(self, path) -> Path:
@@ -464,6 +472,10 @@ class VRVQFile:
             if input_db.size == 0 or len(rw) % input_db.size:
                 raise ValueError("input_db does not match the rows")
             level, kbps = h.get("level"), h.get("target_kbps")
+            max_kbps, packet_frames = h.get("max_kbps"), h.get("packet_frames")
+            if packet_frames is not None and (type(packet_frames) is not int
+                                              or packet_frames < 1):
+                raise ValueError("packet_frames out of range")
         except (KeyError, TypeError, ValueError, UnicodeDecodeError) as e:
             raise RuntimeError(f"{path}: bad .vrvq header ({e})") from None
         payload = len(blob) - 12 - hlen
@@ -484,7 +496,42 @@ class VRVQFile:
         return cls(bitstream=bs, chunk_length=ints["chunk_length"],
                    original_length=ints["original_length"], input_db=torch.from_numpy(input_db),
                    channels=ints["channels"], sample_rate=ints["sample_rate"],
-                   padding=h["padding"], level=level, target_kbps=kbps)
+                   padding=h["padding"], level=level, target_kbps=kbps, max_kbps=max_kbps,
+                   packet_frames=packet_frames)
+
+    def frame_counts(self) -> np.ndarray:
+        """Codes kept per frame, (rows, frames) int64, read from the count planes on the host
+        (a stream without a count plane keeps n_codebooks everywhere)."""
+        bs = self.bitstream
+        if not bs.count_bits:
+            return np.full((bs.rows, bs.frames), bs.n_codebooks, np.int64)
+        words = bs.words.detach().cpu().numpy().view(np.uint32)
+        lo, off, out = _words_of(bs.frames * bs.count_bits), 0, []
+        for n in bs.row_words:
+            out.append(_words_to_fields(words[off:off + lo], bs.count_bits, bs.frames))
+            off += int(n)
+        return np.stack(out)
+
+    def packet_kbps(self, model_sample_rate: int, hop_length: int,
+                    packet_frames: Optional[int] = None) -> np.ndarray:
+        """The realised rate of every packet, (rows, packets) float64 in kbps: its count fields
+        plus its kept codes (no padding) over its own frames, at the frame rate
+        floor(model_sample_rate / hop_length) of kbps_to_budget. Packets are runs of
+        packet_frames frames that restart at every chunk_length, the last of a chunk may be
+        short (default: the file's packet_frames, else chunk_length: one packet per window). Its
+        maximum is the peak rate of the file at that packet length; a file that
+        compress(max_kbps=...) wrote has none above max_kbps at its own packet_frames."""
+        bs = self.bitstream
+        cl = int(self.chunk_length)
+        P = int(packet_frames if packet_frames is not None else self.packet_frames or cl)
+        if P < 1:
+            raise ValueError("packet_kbps: packet_frames must be >= 1")
+        counts = self.frame_counts().reshape(bs.rows, bs.frames // cl, cl)
+        starts = np.arange(0, cl, P)
+        n_f = np.minimum(P, cl - starts)                      # frames of each packet of a chunk
+        bits = np.add.reduceat(counts, starts, axis=2) * bs.code_bits + n_f * bs.count_bits
+        rate = int(model_sample_rate) // int(hop_length)
+        return (bits / n_f * rate / 1000.0).reshape(bs.rows, -1)
 
     def payload_kbps(self, model_sample_rate: int, hop_length: int) -> float:
         """The stream's rate on disk: 32 * sum(row_words) bits over the duration of its

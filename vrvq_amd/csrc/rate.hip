@@ -213,6 +213,278 @@ __global__ __launch_bounds__(RATE_THREADS) void rate_solve_kernel(
                        total_out + g, status + g);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Capped rate control: a packet is a run of P frames of one row (NP = ceil(T / P) per row, the
+// last one short). Launch 1 solves every packet on its own against packet_budget[p] (its cap);
+// launch 2 solves each group's level lambda over bits(min(lambda, cap)) and writes the packets'
+// levels, totals and states. The caps travel from launch 1 to launch 2 in packet_level itself.
+
+// solve_group's bisection over any total: the largest level in [lo, hi] with bits_at(level) <=
+// budget. solve_group keeps its own loop: built on this one, rate_solve_kernel compiles to other
+// code (6 more VGPRs), and a commit that adds a path leaves the existing one as it was.
+// bits_at(level) returns the same total in every thread that shares its barriers or shuffles, so
+// every decision is uniform over them and each runs the same number of calls. The interval
+// [lo_u, hi_u] at least halves per pass and is narrower than 2^31, so the loop ends within 31
+// passes for any input (its bound of 32 is never the reason it ends).
+template <class F>
+__device__ __forceinline__ void bisect_level(F&& bits_at, long long budget, float level_lo,
+                                             float level_hi, float& lvl, long long& tot, int& st) {
+  const long long t_lo = bits_at(level_lo);
+  if (t_lo > budget) {  // every frame costs at least one code
+    st = 1;
+    lvl = level_lo;
+    tot = t_lo;
+  } else {
+    const long long t_hi = bits_at(level_hi);
+    if (t_hi <= budget) {
+      st = 2;
+      lvl = level_hi;
+      tot = t_hi;
+    } else {
+      unsigned lo_u = __float_as_uint(level_lo), hi_u = __float_as_uint(level_hi);
+      tot = t_lo;
+      for (int it = 0; it < 32 && hi_u - lo_u > 1u; ++it) {
+        const unsigned mid = lo_u + ((hi_u - lo_u) >> 1);
+        const long long t_mid = bits_at(__uint_as_float(mid));
+        if (t_mid <= budget) {
+          lo_u = mid;
+          tot = t_mid;
+        } else {
+          hi_u = mid;
+        }
+      }
+      st = 0;
+      lvl = __uint_as_float(lo_u);
+    }
+  }
+}
+
+// A wave holds a packet of up to CAP_KEEP * 64 = 256 frames in registers; a longer one is read
+// again in every pass, 256 frames at a time.
+constexpr int CAP_KEEP = 4;
+
+// Bits of frames x[0..nf) at one level, in every lane of the wave (no barrier). KEEP: the frames
+// are in v[] (NaN past nf).
+template <bool KEEP>
+__device__ __forceinline__ long long packet_bits(const float (&v)[CAP_KEEP],
+                                                 const float* __restrict__ x, int nf, float level,
+                                                 int nq, const long long* cum) {
+  const int lane = threadIdx.x & 63;
+  long long acc = 0;
+  if (KEEP) {
+#pragma unroll
+    for (int k = 0; k < CAP_KEEP; ++k)
+      if (k * 64 < nf) acc += cum[frame_count(v[k], level, nq)];
+  } else {
+    // as group_bits: clamped addresses, the value replaced afterwards, no load under a branch
+    for (long long base = 0; base < nf; base += CAP_KEEP * 64) {
+      float w[CAP_KEEP];
+#pragma unroll
+      for (int k = 0; k < CAP_KEEP; ++k) {
+        const long long f = base + k * 64 + lane;
+        const float val = x[f < nf ? f : nf - 1];
+        w[k] = f < nf ? val : __uint_as_float(0x7fc00000u);  // NaN: 0 bits
+      }
+#pragma unroll
+      for (int k = 0; k < CAP_KEEP; ++k) acc += cum[frame_count(w[k], level, nq)];
+    }
+  }
+  return wave_sum(acc);
+}
+
+// Launch 1: one wave per packet, RATE_WAVES packets per workgroup. Writes the packet's cap, its
+// total at the cap and state 1 (infeasible) or 2: what a row that belongs to no valid group keeps.
+__global__ __launch_bounds__(RATE_THREADS) void rate_caps_kernel(
+    const float* __restrict__ imp, int B, int T, int P, int NP, int nq,
+    const int* __restrict__ bits, const long long* __restrict__ packet_budget, float level_lo,
+    float level_hi, float* __restrict__ packet_level, long long* __restrict__ packet_total,
+    int* __restrict__ packet_status) {
+  __shared__ long long cum[RATE_MAX_NQ + 1];
+  fill_cum(bits, nq, cum);
+  __syncthreads();  // the only barrier: everything below is per wave
+  const long long pk = (long long)blockIdx.x * RATE_WAVES + (threadIdx.x >> 6);
+  if (pk >= (long long)B * NP) return;  // uniform over the wave
+  const long long row = pk / NP;
+  const int p = (int)(pk - row * NP);
+  const int f0 = p * P;  // < T
+  const int nf = min(P, T - f0);
+  const float* x = imp + (size_t)row * T + f0;
+  const int lane = threadIdx.x & 63;
+  const bool keep = nf <= CAP_KEEP * 64;
+  float v[CAP_KEEP];
+#pragma unroll
+  for (int k = 0; k < CAP_KEEP; ++k) {
+    const int f = k * 64 + lane;
+    v[k] = keep && f < nf ? x[f] : __uint_as_float(0x7fc00000u);
+  }
+  const long long budget = packet_budget[p];
+  float lvl;
+  long long tot;
+  int st;
+  if (keep)
+    bisect_level([&](float level) { return packet_bits<true>(v, x, nf, level, nq, cum); }, budget,
+                 level_lo, level_hi, lvl, tot, st);
+  else
+    bisect_level([&](float level) { return packet_bits<false>(v, x, nf, level, nq, cum); },
+                 budget, level_lo, level_hi, lvl, tot, st);
+  if (lane == 0) {
+    packet_level[pk] = lvl;
+    packet_total[pk] = tot;
+    packet_status[pk] = st == 1 ? 1 : 2;
+  }
+}
+
+// Bits of the group with every element at min(level, the cap of its packet), in every thread.
+// KEEP: values and caps are in v[] and c[]; else the values are at x[0..n) (rows of T frames) and
+// the caps at cap[row * NP + t / P], both read again.
+template <bool KEEP>
+__device__ __forceinline__ long long group_bits_capped(const float (&v)[RATE_KEEP],
+                                                       const float (&c)[RATE_KEEP],
+                                                       const float* __restrict__ x,
+                                                       const float* cap, long long n, int T, int P,
+                                                       int NP, float level, int nq,
+                                                       const long long* cum, long long* part) {
+  long long acc = 0;
+  if (KEEP) {
+#pragma unroll
+    for (int k = 0; k < RATE_KEEP; ++k)
+      if ((long long)k * RATE_THREADS < n)
+        acc += cum[frame_count(v[k], fminf(level, c[k]), nq)];
+  } else {
+    // (row, t) of the thread's element moves on by 256 elements per slot without a division
+    // (unsigned: t + 256 stays below 2^32 for any T)
+    const unsigned uT = T, uP = P, dq = RATE_THREADS / uT, dr = RATE_THREADS % uT;
+    long long row = threadIdx.x / uT;
+    unsigned t = threadIdx.x % uT;
+    for (long long base = 0; base < n; base += (long long)RATE_KEEP * RATE_THREADS) {
+      float w[RATE_KEEP], cw[RATE_KEEP];
+#pragma unroll
+      for (int k = 0; k < RATE_KEEP; ++k) {
+        const long long e = base + k * RATE_THREADS + (long long)threadIdx.x;
+        const float val = x[e < n ? e : n - 1];
+        cw[k] = cap[e < n ? row * NP + t / uP : 0];
+        w[k] = e < n ? val : __uint_as_float(0x7fc00000u);  // NaN: 0 bits
+        row += dq;
+        t += dr;
+        if (t >= uT) {
+          t -= uT;
+          ++row;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < RATE_KEEP; ++k)
+        acc += cum[frame_count(w[k], fminf(level, cw[k]), nq)];
+    }
+  }
+  return block_sum(acc, part);
+}
+
+// Launch 2: one workgroup per group, as rate_solve_kernel, then one wave per packet of the
+// group's rows for the packet outputs. Groups that share rows leave those rows' packet outputs
+// to whichever workgroup writes last.
+__global__ __launch_bounds__(RATE_THREADS) void rate_solve_capped_kernel(
+    const float* __restrict__ imp, int B, int T, int P, int NP, int nq,
+    const int* __restrict__ bits, const int* __restrict__ group_off,
+    const long long* __restrict__ budget, float level_lo, float level_hi,
+    float* __restrict__ level_out, long long* __restrict__ total_out, int* __restrict__ status,
+    float* packet_level, long long* packet_total, int* packet_status) {
+  __shared__ long long cum[RATE_MAX_NQ + 1];
+  __shared__ long long part[2][RATE_WAVES];
+  const int g = blockIdx.x;
+  const int r0 = group_off[g], r1 = group_off[g + 1];
+  // uniform over the workgroup and before the first barrier, as in rate_solve_kernel
+  if (r0 < 0 || r1 < r0 || r1 > B) {
+    if (threadIdx.x == 0) {
+      level_out[g] = level_lo;
+      total_out[g] = 0;
+      status[g] = -1;
+    }
+    return;
+  }
+  if (r0 == r1) {
+    if (threadIdx.x == 0) {
+      level_out[g] = level_hi;
+      total_out[g] = 0;
+      status[g] = 2;
+    }
+    return;
+  }
+  fill_cum(bits, nq, cum);
+  const long long n = (long long)(r1 - r0) * T;
+  const float* x = imp + (size_t)r0 * T;
+  float* cap = packet_level + (size_t)r0 * NP;  // launch 1 left the caps here
+  float v[RATE_KEEP], c[RATE_KEEP];
+  const bool keep = n <= (long long)RATE_KEEP * RATE_THREADS;
+#pragma unroll
+  for (int k = 0; k < RATE_KEEP; ++k) {
+    const int e = k * RATE_THREADS + (int)threadIdx.x;  // < 4096
+    const bool in = keep && e < n;
+    v[k] = in ? x[e] : __uint_as_float(0x7fc00000u);  // NaN: no codes, cum[0] = 0 bits
+    c[k] = in ? cap[(long long)(e / T) * NP + (e % T) / P] : level_lo;
+  }
+  __syncthreads();  // cum
+  int call = 0, st;
+  float lvl;
+  long long tot;
+  if (keep)
+    bisect_level(
+        [&](float level) {
+          return group_bits_capped<true>(v, c, x, cap, n, T, P, NP, level, nq, cum,
+                                         part[call++ & 1]);
+        },
+        budget[g], level_lo, level_hi, lvl, tot, st);
+  else
+    bisect_level(
+        [&](float level) {
+          return group_bits_capped<false>(v, c, x, cap, n, T, P, NP, level, nq, cum,
+                                          part[call++ & 1]);
+        },
+        budget[g], level_lo, level_hi, lvl, tot, st);
+  if (threadIdx.x == 0) {
+    level_out[g] = lvl;
+    total_out[g] = tot;
+    status[g] = st;
+  }
+  // Packet outputs. Every thread passed the barrier of the last block_sum after its last read of
+  // a cap, so the caps may be overwritten now; each packet is read and written by one wave. The
+  // wave's (row, p) moves on by RATE_WAVES packets without a division.
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long npk = (long long)(r1 - r0) * NP;
+  const int dq = RATE_WAVES / NP, dr = RATE_WAVES % NP;
+  long long row = wave / NP;
+  int p = wave % NP;
+  const float none[CAP_KEEP] = {};  // packet_bits<false> reads the frames, not this
+  for (long long k = wave; k < npk; k += RATE_WAVES) {
+    const int f0 = p * P;
+    const float cp = cap[k];
+    const int st0 = packet_status[(size_t)r0 * NP + k];
+    const float l = fminf(lvl, cp);
+    const long long t_p =
+        packet_bits<false>(none, x + (size_t)row * T + f0, min(P, T - f0), l, nq, cum);
+    if (lane == 0) {
+      cap[k] = l;
+      packet_total[(size_t)r0 * NP + k] = t_p;
+      packet_status[(size_t)r0 * NP + k] = st0 == 1 ? 1 : (cp < lvl ? 2 : 0);
+    }
+    row += dq;
+    p += dr;
+    if (p >= NP) {
+      p -= NP;
+      ++row;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void scale_imp_packets_kernel(
+    const float* __restrict__ imp, long long n, int T, int P, int NP,
+    const float* __restrict__ packet_level, float* __restrict__ out) {
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n;
+       e += (long long)gridDim.x * 256) {
+    const long long row = e / T;
+    out[e] = imp[e] * packet_level[row * NP + (int)(e - row * T) / P];
+  }
+}
+
 __global__ __launch_bounds__(256) void scale_imp_rows_kernel(const float* __restrict__ imp,
                                                              long long n, int T,
                                                              const float* __restrict__ levels,
@@ -250,6 +522,46 @@ extern "C" int vrvq_rate_solve(const float* imp, int batch, int frames, int nq, 
   hipLaunchKernelGGL(rate_solve_kernel, dim3(n_groups), dim3(RATE_THREADS), 0, as_stream(stream),
                      imp, batch, frames, nq, bits, group_off, budget, level_lo, level_hi,
                      level_out, total_out, status);
+  return vrvq_launch_status();
+}
+
+extern "C" int vrvq_rate_solve_capped(const float* imp, int batch, int frames, int nq,
+                                      const int* bits, const int* group_off, int n_groups,
+                                      const long long* budget, const long long* packet_budget,
+                                      int packet_frames, float level_lo, float level_hi,
+                                      float* level_out, long long* total_out, int* status,
+                                      float* packet_level, long long* packet_total,
+                                      int* packet_status, vrvq_stream_t stream) {
+  VRVQ_CHECK_ARG(imp && bits && group_off && budget && level_out && total_out && status);
+  VRVQ_CHECK_ARG(packet_budget && packet_level && packet_total && packet_status);
+  VRVQ_CHECK_ARG(batch > 0 && frames > 0 && n_groups > 0 && nq > 0 && nq <= RATE_MAX_NQ);
+  VRVQ_CHECK_ARG(packet_frames >= 1);
+  VRVQ_CHECK_ARG(level_range_ok(level_lo, level_hi));
+  const int np = (frames - 1) / packet_frames + 1;
+  const long long wgs = ((long long)batch * np + RATE_WAVES - 1) / RATE_WAVES;
+  VRVQ_CHECK_ARG(wgs <= 0x7fffffffLL);
+  hipLaunchKernelGGL(rate_caps_kernel, dim3((unsigned)wgs), dim3(RATE_THREADS), 0,
+                     as_stream(stream), imp, batch, frames, packet_frames, np, nq, bits,
+                     packet_budget, level_lo, level_hi, packet_level, packet_total, packet_status);
+  const int rc = vrvq_launch_status();
+  if (rc) return rc;
+  hipLaunchKernelGGL(rate_solve_capped_kernel, dim3(n_groups), dim3(RATE_THREADS), 0,
+                     as_stream(stream), imp, batch, frames, packet_frames, np, nq, bits, group_off,
+                     budget, level_lo, level_hi, level_out, total_out, status, packet_level,
+                     packet_total, packet_status);
+  return vrvq_launch_status();
+}
+
+extern "C" int vrvq_scale_imp_packets(const float* imp, int batch, int frames,
+                                      const float* packet_level, int packet_frames, float* out,
+                                      vrvq_stream_t stream) {
+  VRVQ_CHECK_ARG(imp && packet_level && out && batch > 0 && frames > 0 && packet_frames >= 1);
+  const long long n = (long long)batch * frames;
+  long long g = (n + 255) / 256;
+  if (g > 65536) g = 65536;
+  hipLaunchKernelGGL(scale_imp_packets_kernel, dim3((unsigned)g), dim3(256), 0, as_stream(stream),
+                     imp, n, frames, packet_frames, (frames - 1) / packet_frames + 1, packet_level,
+                     out);
   return vrvq_launch_status();
 }
 

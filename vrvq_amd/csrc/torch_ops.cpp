@@ -744,6 +744,66 @@ Tensor scale_imp_rows(const Tensor& imp, const Tensor& levels) {
   return out;
 }
 
+// A cap on every packet of packet_frames frames next to the groups' budgets (include/vrvq.h
+// "Capped rate control"): (level, total, status) per group, (packet_level, packet_total,
+// packet_status) (B, NP).
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> rate_solve_capped(
+    const Tensor& imp, const Tensor& bits, const Tensor& group_off, const Tensor& budget,
+    const Tensor& packet_budget, int64_t packet_frames, double level_lo, double level_hi) {
+  const int64_t B = imp_rows(imp, "rate_solve_capped"), T = imp.size(-1);
+  check_on(bits, imp, "bits", at::kInt);
+  check_on(group_off, imp, "group_off", at::kInt);
+  check_on(budget, imp, "budget", at::kLong);
+  check_on(packet_budget, imp, "packet_budget", at::kLong);
+  TORCH_CHECK(bits.dim() == 1 && group_off.dim() == 1 && group_off.numel() >= 2,
+              "rate_solve_capped: bits (nq,), group_off (G + 1,)");
+  const int64_t G = group_off.numel() - 1;
+  TORCH_CHECK(budget.dim() == 1 && budget.numel() == G,
+              "rate_solve_capped: one budget per group");
+  TORCH_CHECK(packet_frames >= 1 && packet_frames < (1LL << 31),
+              "rate_solve_capped: packet_frames must be >= 1");
+  const int64_t NP = (T - 1) / packet_frames + 1;
+  TORCH_CHECK(packet_budget.dim() == 1 && packet_budget.numel() == NP,
+              "rate_solve_capped: one packet_budget per packet of a row (", NP, ")");
+  c10::DeviceGuard guard(imp.device());
+  Tensor level = at::empty({G}, imp.options());
+  Tensor total = at::empty({G}, imp.options().dtype(at::kLong));
+  Tensor status = at::empty({G}, imp.options().dtype(at::kInt));
+  Tensor p_level = at::empty({B, NP}, imp.options());
+  Tensor p_total = at::empty({B, NP}, imp.options().dtype(at::kLong));
+  Tensor p_status = at::empty({B, NP}, imp.options().dtype(at::kInt));
+  check_rc(vrvq_rate_solve_capped(
+               imp.data_ptr<float>(), (int)B, (int)T, (int)bits.numel(), bits.data_ptr<int>(),
+               group_off.data_ptr<int>(), (int)G,
+               reinterpret_cast<const long long*>(budget.data_ptr<int64_t>()),
+               reinterpret_cast<const long long*>(packet_budget.data_ptr<int64_t>()),
+               (int)packet_frames, (float)level_lo, (float)level_hi, level.data_ptr<float>(),
+               reinterpret_cast<long long*>(total.data_ptr<int64_t>()), status.data_ptr<int>(),
+               p_level.data_ptr<float>(),
+               reinterpret_cast<long long*>(p_total.data_ptr<int64_t>()),
+               p_status.data_ptr<int>(), stream_of(imp)),
+           "vrvq_rate_solve_capped");
+  return {level, total, status, p_level, p_total, p_status};
+}
+
+// imp_map times the level of each frame's packet: packet_level (B, NP), NP = ceil(T / P).
+Tensor scale_imp_packets(const Tensor& imp, const Tensor& packet_level, int64_t packet_frames) {
+  const int64_t B = imp_rows(imp, "scale_imp_packets"), T = imp.size(-1);
+  check_on(packet_level, imp, "packet_level");
+  TORCH_CHECK(packet_frames >= 1 && packet_frames < (1LL << 31),
+              "scale_imp_packets: packet_frames must be >= 1");
+  const int64_t NP = (T - 1) / packet_frames + 1;
+  TORCH_CHECK(packet_level.numel() == B * NP,
+              "scale_imp_packets: packet_level must be (B, ", NP, ")");
+  c10::DeviceGuard guard(imp.device());
+  Tensor out = at::empty_like(imp);
+  check_rc(vrvq_scale_imp_packets(imp.data_ptr<float>(), (int)B, (int)T,
+                                  packet_level.data_ptr<float>(), (int)packet_frames,
+                                  out.data_ptr<float>(), stream_of(imp)),
+           "vrvq_scale_imp_packets");
+  return out;
+}
+
 // --------------------------------------------------------------------------- distortion metrics
 // SI-SDR / SI-SNR / SNR / L1 of every row of est against row r % B of ref (include/vrvq.h
 // "Distortion metrics"; models/utils.py:91-129 cal_metrics on the device). est (R, T) or
@@ -1541,6 +1601,11 @@ TORCH_LIBRARY(vrvq, m) {
       "float level_hi) -> (Tensor, Tensor, Tensor)");
   m.def("scale_imp_rows(Tensor imp, Tensor levels) -> Tensor");
   m.def(
+      "rate_solve_capped(Tensor imp, Tensor bits, Tensor group_off, Tensor budget, "
+      "Tensor packet_budget, int packet_frames, float level_lo, float level_hi) "
+      "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("scale_imp_packets(Tensor imp, Tensor packet_level, int packet_frames) -> Tensor");
+  m.def(
       "signal_metrics(Tensor est, Tensor ref, Tensor? lengths) "
       "-> (Tensor metrics, Tensor moments)");
   m.def(
@@ -1630,6 +1695,8 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("rate_curve", &rate_curve); \
   m.impl("rate_solve", &rate_solve); \
   m.impl("scale_imp_rows", &scale_imp_rows); \
+  m.impl("rate_solve_capped", &rate_solve_capped); \
+  m.impl("scale_imp_packets", &scale_imp_packets); \
   m.impl("signal_metrics", &signal_metrics); \
   m.impl("spectral_distance", &spectral_distance); \
   m.impl("spectral_distance_grad", &spectral_distance_grad); \

@@ -335,15 +335,40 @@ class ResidualVectorQuantize(nn.Module):
 
 
 def _check_rate_args(vbr: bool, training: bool, n_quantizers, level, target_kbps,
-                     default_level) -> bool:
+                     default_level, max_kbps=None, packet_frames=None, frames=None) -> bool:
     """True when the call asks for rate control: a per-clip level (a tensor of one dimension or
     more) or target_kbps. Both need a VBR quantizer in eval mode without n_quantizers, and they
     exclude each other; anything else raises ValueError before a kernel runs. A scalar level
-    alone is today's call and is not touched."""
+    alone is today's call and is not touched.
+
+    max_kbps (a cap on every packet of packet_frames frames) needs target_kbps and packet_frames;
+    a (B, NP) level (the caller's own level per packet) needs packet_frames and, where the frame
+    count is known (`frames`: the quantizer knows it, encode does not before its encoder ran),
+    NP = ceil(frames / packet_frames); packet_frames is an integer >= 1 and needs one of the
+    two."""
     per_clip = torch.is_tensor(level) and level.dim() > 0
+    per_packet = per_clip and level.dim() == 2
+    if max_kbps is not None and target_kbps is None:
+        raise ValueError("max_kbps needs target_kbps (a cap without an average has no solve)")
+    if max_kbps is not None and packet_frames is None:
+        raise ValueError("max_kbps needs packet_frames, the frames a packet spans")
+    if per_packet and packet_frames is None and target_kbps is None:
+        raise ValueError("a (B, NP) level needs packet_frames")
+    if packet_frames is not None:
+        if isinstance(packet_frames, bool) or packet_frames != int(packet_frames) \
+                or packet_frames < 1:
+            raise ValueError(f"packet_frames must be an integer >= 1, not {packet_frames!r}")
+        if max_kbps is None and not per_packet:
+            raise ValueError("packet_frames needs max_kbps or a (B, NP) level")
+        if per_packet and target_kbps is None and frames is not None \
+                and level.shape[1] != (frames - 1) // int(packet_frames) + 1:
+            raise ValueError(f"a (B, NP) level needs NP = "
+                             f"{(frames - 1) // int(packet_frames) + 1} packets of "
+                             f"{packet_frames} frames for {frames} frames, not {level.shape[1]}")
     if target_kbps is None and not per_clip:
         return False
-    what = "target_kbps" if target_kbps is not None else "a per-clip level"
+    what = "max_kbps" if max_kbps is not None else "target_kbps" if target_kbps is not None \
+        else "a per-packet level" if per_packet else "a per-clip level"
     if target_kbps is not None and (per_clip or not (
             level is default_level or (default_level is not None and level == default_level))):
         raise ValueError("give either level or target_kbps, not both")
@@ -378,15 +403,24 @@ class VBRResidualVectorQuantize(ResidualVectorQuantize):
 
     def forward(self, z: torch.Tensor, n_quantizers: int = None, feat_enc: torch.Tensor = None,
                 level: float = None, want_z_q_is: bool = True, target_kbps=None,
-                sample_rate: int = None, hop_length: int = None):
+                sample_rate: int = None, hop_length: int = None, max_kbps=None,
+                packet_frames: int = None):
         """`level` may be a (B,) float32 tensor, one level per clip (eval only): each row of the
         importance map is scaled by its own level and the RVQ runs at level 1.0, which gives the
         scalar-level expression for that row bit for bit. `target_kbps` (a number or one per
         clip) solves each clip's level within [level_min, level_max] on the device
         (utils.solve_levels) and adds "level", "bpf" and "rate_status" (B,) to the dict; it needs
-        the codec's sample_rate and hop_length (DAC_VRVQ.encode passes them)."""
+        the codec's sample_rate and hop_length (DAC_VRVQ.encode passes them).
+
+        `max_kbps` with `packet_frames` (and target_kbps) also caps every packet of packet_frames
+        frames of a clip (utils.solve_levels_capped): the levels then vary inside a clip, "level"
+        is the level of the packets their cap does not bind, and the dict also holds
+        "packet_level", "packet_bits" and "packet_status" (B, NP). `level` may be a (B, NP)
+        float32 tensor with `packet_frames`: the caller's own level per packet. Either way the
+        map is scaled per packet and the RVQ launch is the one of a per-clip level."""
         rate_control = _check_rate_args(True, self.training, n_quantizers, level, target_kbps,
-                                        default_level=None)
+                                        None, max_kbps, packet_frames,
+                                        frames=z.shape[-1] if torch.is_tensor(z) else None)
         if n_quantizers is None and level is None and target_kbps is None:
             raise AssertionError("level must be specified in VBR mode")
         if self.training:
@@ -418,16 +452,32 @@ class VBRResidualVectorQuantize(ResidualVectorQuantize):
                     if sample_rate is None or hop_length is None:
                         raise ValueError("target_kbps needs sample_rate and hop_length")
                     from . import utils
-                    levels, bpf, status = utils.solve_levels(
-                        imp, target_kbps, nq=nq, sample_rate=sample_rate, hop_length=hop_length,
-                        level_min=self.level_min, level_max=self.level_max)
-                    rate = {"level": levels, "bpf": bpf, "rate_status": status}
+                    kw = dict(nq=nq, sample_rate=sample_rate, hop_length=hop_length,
+                              level_min=self.level_min, level_max=self.level_max)
+                    if max_kbps is not None:
+                        r = utils.solve_levels_capped(imp, target_kbps, max_kbps, packet_frames,
+                                                      **kw)
+                        rate = {"level": r["level"], "bpf": r["bpf"], "rate_status": r["status"],
+                                "packet_level": r["packet_level"],
+                                "packet_bits": r["packet_bits"],
+                                "packet_status": r["packet_status"]}
+                        levels = r["packet_level"]
+                    else:
+                        levels, bpf, status = utils.solve_levels(imp, target_kbps, **kw)
+                        rate = {"level": levels, "bpf": bpf, "rate_status": status}
                 else:
-                    if level.shape != (B,) or level.dtype != torch.float32:
-                        raise ValueError(f"a tensor level must be ({B},) float32, one per clip")
+                    NP = 1 if packet_frames is None else (T - 1) // int(packet_frames) + 1
+                    if level.shape not in ((B,), (B, NP)) or level.dtype != torch.float32 or (
+                            level.dim() == 2 and packet_frames is None):
+                        raise ValueError(f"a tensor level must be ({B},) float32, one per clip, "
+                                         f"or ({B}, NP) with packet_frames, one per packet")
                     levels = level.to(imp.device).contiguous()
-                # the row's own level here, level 1.0 (an exact product) in the RVQ launch
-                imp, lvl = ops.scale_imp_rows(imp, levels), 1.0
+                # the row's or the packet's own level here, level 1.0 (an exact product) in the
+                # RVQ launch
+                if levels.dim() == 2:
+                    imp, lvl = ops.scale_imp_packets(imp, levels, int(packet_frames)), 1.0
+                else:
+                    imp, lvl = ops.scale_imp_rows(imp, levels), 1.0
             else:
                 lvl = float(level)
         else:
@@ -601,7 +651,8 @@ class DAC_VRVQ(nn.Module, CodecMixin):
         return nn.functional.pad(audio_data, (0, right_pad))
 
     def encode(self, audio_data: torch.Tensor, n_quantizers: int = None, level: int = 1,
-               want_z_q_is: bool = True, target_kbps=None):
+               want_z_q_is: bool = True, target_kbps=None, max_kbps=None,
+               packet_frames: int = None):
         """models/dac_vrvq.py:176-213. Returns the quantizer's output dict.
 
         `want_z_q_is=False` skips materialising the (B, Nq, D, T) per-codebook tensor when the
@@ -612,9 +663,16 @@ class DAC_VRVQ(nn.Module, CodecMixin):
         tensor, one level per clip, and `target_kbps` (a number or one per clip) has each clip's
         level solved on the device within [level_min, level_max]; the dict then also holds
         "level", "bpf" and "rate_status" (VBRResidualVectorQuantize.forward). Neither makes a
-        host sync, so both run under graph capture."""
+        host sync, so both run under graph capture.
+
+        A cap on the short-term rate: `max_kbps` with `packet_frames` (next to target_kbps) keeps
+        every packet of packet_frames frames of a clip within max_kbps while the clip meets
+        target_kbps, with levels that vary inside the clip; the dict then also holds
+        "packet_level", "packet_bits" and "packet_status" (B, NP), NP = ceil(frames /
+        packet_frames). `level` may be a (B, NP) float32 tensor together with packet_frames, the
+        caller's own level per packet. No host sync either."""
         rate_control = _check_rate_args(self.model_type == "VBR", self.training, n_quantizers,
-                                        level, target_kbps, default_level=1)
+                                        level, target_kbps, 1, max_kbps, packet_frames)
         ev = not self.training and not self.encoder.valid
         # the projection epilogue computes the stages the quantizer runs: all of them, or a CBR
         # prefix (n_quantizers < Nq; a VBR model raises for one in its quantizer)
@@ -632,7 +690,8 @@ class DAC_VRVQ(nn.Module, CodecMixin):
         if rate_control:
             return self.quantizer(z, None, feat, None if target_kbps is not None else level,
                                   want_z_q_is=want_z_q_is, target_kbps=target_kbps,
-                                  sample_rate=self.sample_rate, hop_length=self.hop_length)
+                                  sample_rate=self.sample_rate, hop_length=self.hop_length,
+                                  max_kbps=max_kbps, packet_frames=packet_frames)
         return self.quantizer(z, n_quantizers, feat, level, want_z_q_is=want_z_q_is)
 
     def decode(self, z: torch.Tensor):
@@ -640,21 +699,25 @@ class DAC_VRVQ(nn.Module, CodecMixin):
         return self.decoder(z.contiguous())
 
     def forward(self, audio_data: torch.Tensor, sample_rate: int = None, n_quantizers: int = None,
-                level: int = 1, target_kbps=None):
-        """models/dac_vrvq.py:222-252. `level` as a (B,) tensor and `target_kbps` as in encode;
-        with target_kbps the dict also holds "level", "bpf" and "rate_status"."""
+                level: int = 1, target_kbps=None, max_kbps=None, packet_frames: int = None):
+        """models/dac_vrvq.py:222-252. `level` as a (B,) or (B, NP) tensor, `target_kbps`,
+        `max_kbps` and `packet_frames` as in encode; with target_kbps the dict also holds "level",
+        "bpf" and "rate_status", with max_kbps also "packet_level", "packet_bits" and
+        "packet_status"."""
         rate_control = _check_rate_args(self.model_type == "VBR", self.training, n_quantizers,
-                                        level, target_kbps, default_level=1)
+                                        level, target_kbps, 1, max_kbps, packet_frames)
         length = audio_data.shape[-1]
         audio_data = self.preprocess(audio_data, sample_rate)
         if rate_control:
-            out = self.encode(audio_data, n_quantizers, level, target_kbps=target_kbps)
+            out = self.encode(audio_data, n_quantizers, level, target_kbps=target_kbps,
+                              max_kbps=max_kbps, packet_frames=packet_frames)
         else:
             out = self.encode(audio_data, n_quantizers, level) if self.model_type == "VBR" \
                 else self.encode(audio_data, n_quantizers)
         z_q = out["z_q"]
         x = self.decode(z_q)
-        rate = {k: out[k] for k in ("level", "bpf", "rate_status") if k in out}
+        rate = {k: out[k] for k in ("level", "bpf", "rate_status", "packet_level", "packet_bits",
+                                    "packet_status") if k in out}
         return {
             "audio": x[..., :length],
             "z": z_q,

@@ -312,6 +312,25 @@ def scale_imp_rows(imp: torch.Tensor, levels: torch.Tensor) -> torch.Tensor:
     return _ops().scale_imp_rows(imp, levels)
 
 
+def rate_solve_capped(imp: torch.Tensor, bits: torch.Tensor, group_off: torch.Tensor,
+                      budget: torch.Tensor, packet_budget: torch.Tensor, packet_frames: int,
+                      level_lo: float, level_hi: float):
+    """rate_solve with a cap on every packet of packet_frames frames of a row: packet_budget
+    (NP,) int64, NP = ceil(T / packet_frames), the bits packet p of any row may take. Returns
+    (level (G,), total (G,), status (G,)) as rate_solve, for the level the group's uncapped
+    packets run at, and (packet_level (B, NP) float32, packet_total (B, NP) int64, packet_status
+    (B, NP) int32: 0 at the group's level, 1 infeasible, 2 at its cap); two launches, no host
+    sync (include/vrvq.h vrvq_rate_solve_capped)."""
+    return _ops().rate_solve_capped(imp, bits, group_off, budget, packet_budget,
+                                    int(packet_frames), float(level_lo), float(level_hi))
+
+
+def scale_imp_packets(imp: torch.Tensor, packet_level: torch.Tensor,
+                      packet_frames: int) -> torch.Tensor:
+    """imp[b, t] * packet_level[b, t // packet_frames]: one fp32 rounding per element."""
+    return _ops().scale_imp_packets(imp, packet_level, int(packet_frames))
+
+
 def signal_metrics(est: torch.Tensor, ref: torch.Tensor,
                    lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Distortion of every row of est (R, T) or (R, 1, T) against row r % B of ref (B, T) or
@@ -584,6 +603,19 @@ def _register_fakes():
 
     @reg("vrvq::scale_imp_rows")
     def _(imp, levels):
+        return torch.empty_like(imp)
+
+    @reg("vrvq::rate_solve_capped")
+    def _(imp, bits, group_off, budget, packet_budget, packet_frames, level_lo, level_hi):
+        G, B = group_off.shape[0] - 1, imp.shape[0]
+        NP = (imp.shape[-1] - 1) // packet_frames + 1
+        return (f32(imp, (G,)), imp.new_empty((G,), dtype=torch.int64),
+                imp.new_empty((G,), dtype=torch.int32), f32(imp, (B, NP)),
+                imp.new_empty((B, NP), dtype=torch.int64),
+                imp.new_empty((B, NP), dtype=torch.int32))
+
+    @reg("vrvq::scale_imp_packets")
+    def _(imp, packet_level, packet_frames):
         return torch.empty_like(imp)
 
     @reg("vrvq::signal_metrics")

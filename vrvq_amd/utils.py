@@ -126,28 +126,83 @@ def solve_levels(imp_map: torch.Tensor, target_kbps, *, nq: int, sample_rate: in
     each group's budget on the host before the solve, so codes + side information fit
     target_kbps. A budget that goes negative gives status 1. The returned bpf counts codes only."""
     imp = _imp_rows(imp_map)
-    B, T = imp.shape
     if level_min is None or level_max is None:
         raise ValueError("solve_levels: level_min and level_max are required")
+    off, budget, frames = _rate_groups(imp, target_kbps, pooled, sample_rate, hop_length,
+                                       side_bits_per_frame, "solve_levels")
+    levels, total, status = ops.rate_solve(imp, _bits_table(bits_per_codebook, nq, imp.device),
+                                           off, budget, level_min, level_max)
+    return levels, (total.to(torch.float64) / frames).to(torch.float32), status
+
+
+def _rate_groups(imp, target_kbps, pooled, sample_rate, hop_length, side_bits_per_frame, fn):
+    """(group_off (G + 1,) int32, budget (G,) int64, frames per group) of a solve over the rows
+    of imp (B, T): one group per row, or all rows pooled."""
+    B, T = imp.shape
     if torch.is_tensor(target_kbps) or isinstance(target_kbps, np.ndarray):
         target_kbps = target_kbps.tolist()
     scalar = not isinstance(target_kbps, (list, tuple))
     if pooled:
         if not scalar:
-            raise ValueError("solve_levels: a pooled solve takes one target_kbps")
+            raise ValueError(f"{fn}: a pooled solve takes one target_kbps")
         budgets, frames = [kbps_to_budget(target_kbps, B * T, sample_rate, hop_length)], B * T
         off = _device_const([0, B], torch.int32, imp.device)
     else:
         ks = [target_kbps] * B if scalar else list(target_kbps)
         if len(ks) != B:
-            raise ValueError(f"solve_levels: {len(ks)} targets for {B} clips")
+            raise ValueError(f"{fn}: {len(ks)} targets for {B} clips")
         budgets, frames = [kbps_to_budget(k, T, sample_rate, hop_length) for k in ks], T
         off = torch.arange(B + 1, dtype=torch.int32, device=imp.device)
     budget = _device_const(net_budgets(budgets, frames, side_bits_per_frame), torch.int64,
                            imp.device)
-    levels, total, status = ops.rate_solve(imp, _bits_table(bits_per_codebook, nq, imp.device),
-                                           off, budget, level_min, level_max)
-    return levels, (total.to(torch.float64) / frames).to(torch.float32), status
+    return off, budget, frames
+
+
+def packets_of(frames: int, packet_frames: int) -> int:
+    """Packets of packet_frames frames in a row of `frames` frames (the last may be short)."""
+    return (int(frames) - 1) // int(packet_frames) + 1
+
+
+def solve_levels_capped(imp_map: torch.Tensor, target_kbps, max_kbps: float, packet_frames: int,
+                        *, nq: int, sample_rate: int, hop_length: int, level_min: float,
+                        level_max: float, bits_per_codebook=10, pooled: bool = False,
+                        side_bits_per_frame: int = 0):
+    """solve_levels with a cap on the short-term rate: no packet of `packet_frames` consecutive
+    frames of a clip (the last packet of a clip may be shorter) exceeds `max_kbps`, and each clip
+    (or, pooled, the batch) stays within `target_kbps`. A packet that its cap binds runs at the
+    largest level that fits the cap; all other packets of a group share the largest level at which
+    the group still meets its budget, so the bits the capped packets give up go to the others
+    (include/vrvq.h vrvq_rate_solve_capped; two launches, no host sync for a number or a host
+    sequence of targets).
+
+    Budgets are kbps_to_budget's over each group's and each packet's own frame count (the short
+    last packet gets a pro-rata budget), both less side_bits_per_frame per frame. Returns a dict
+    of device tensors: "level" (G,) float32, the level of the group's uncapped packets, "bpf" (G,)
+    float32 (codes only), "status" (G,) int32 as solve_levels; "packet_level" (B, NP) float32,
+    "packet_bits" (B, NP) int64, "packet_status" (B, NP) int32 (0 at the group's level, 1
+    infeasible: over max_kbps even at level_min, where it runs; 2 held by its cap)."""
+    imp = _imp_rows(imp_map)
+    T = imp.shape[1]
+    if level_min is None or level_max is None:
+        raise ValueError("solve_levels_capped: level_min and level_max are required")
+    P = int(packet_frames)
+    if P < 1 or P != packet_frames:
+        raise ValueError("solve_levels_capped: packet_frames must be an integer >= 1")
+    off, budget, frames = _rate_groups(imp, target_kbps, pooled, sample_rate, hop_length,
+                                       side_bits_per_frame, "solve_levels_capped")
+    NP = packets_of(T, P)
+    sizes = (min(P, T), T - (NP - 1) * P)                     # a full packet, the last one
+    full, tail = (net_budgets([kbps_to_budget(max_kbps, n, sample_rate, hop_length)], n,
+                              side_bits_per_frame)[0] for n in sizes)
+    packet_budget = torch.full((NP,), full, dtype=torch.int64, device=imp.device)
+    if tail != full:
+        packet_budget[NP - 1:].fill_(tail)                    # fills only: capturable
+    level, total, status, p_level, p_total, p_status = ops.rate_solve_capped(
+        imp, _bits_table(bits_per_codebook, nq, imp.device), off, budget, packet_budget, P,
+        level_min, level_max)
+    return {"level": level, "bpf": (total.to(torch.float64) / frames).to(torch.float32),
+            "status": status, "packet_level": p_level, "packet_bits": p_total,
+            "packet_status": p_status}
 
 
 def masked_sum(z_q_is: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
