@@ -273,6 +273,10 @@ int vrvq_pack_convt1d_weight(const float* w, int cin, int cout, int stride, int 
  * qb [nq][d]. */
 int vrvq_rvq_cross_prep(const float* w_in_t, const float* w_out, const float* b_out, int nq,
                         int dim, int cdim, float* mcol, float* qb, vrvq_stream_t stream);
+/* The same with every entry accumulated in fp64 and rounded once (the training step: the fp32
+ * chain's 1e-6 of |M| dominates the error of the quantizer's gradients). */
+int vrvq_rvq_cross_prep_precise(const float* w_in_t, const float* w_out, const float* b_out, int nq,
+                                int dim, int cdim, float* mcol, float* qb, vrvq_stream_t stream);
 
 /* Once per weight version: cbf[i][w][l][t][h] = cbn[i][w*N/8 + 16t + (l&15)][4h + (l>>4)]. */
 int vrvq_rvq_frag(const float* cbn, int nq, int ncode, int cdim, float* cbf,

@@ -11,8 +11,15 @@ Bar: seed-controlled draws bit-exact, codes bit-exact, every gradient tensor wit
 relative (L2 norm of the difference over the L2 norm of the reference, per tensor); the weight
 gradients and the adjoint convs' input gradients also per element (fp32_bar: max-abs below 1e-5
 and within 4x torch fp32's own error + 2e-7). The backward kernels' shape edges are in
-test_gpu_backward_edges.py."""
-import math
+test_gpu_backward_edges.py.
+
+The quantizer's bars: here, the three gradient sources added (dL/dz_q + 0.25 commitment +
+codebook), each gradient as one tensor at 1e-4 L2 (test_rvq_backward_vs_torch64, the module-level
+tests, the generator fixtures) -- the whole-path and reference-parity checks. Per source, per
+stage and per element (4 e32 + 2e-7, exact zeros, the codebook gradient's reduction bar, nq = 1 /
+8 / 32 / 33, N = 256 / 768, decaying residuals, many hits per row) and the mask STE per element
+are in test_gpu_rvq_backward.py; the fp64 loop `rvq64` and `logcosh64` used here live with those
+references in rvq_grad_ref.py."""
 
 import numpy as np
 import pytest
@@ -21,6 +28,7 @@ import torch.nn.functional as F
 
 import rvq_ref as R
 import vrvq_amd
+from rvq_grad_ref import logcosh64, rvq64
 from conftest import load_golden, rel_err
 from vrvq_amd import ops, train
 from vrvq_amd.recipe import load_recipe
@@ -251,19 +259,6 @@ def test_wgrad_c_abi_in_kernel_snake(m, c, k, stride, pad, dil, T):
 
 
 # ------------------------------------------------------------------ mask STE
-def logcosh64(alpha, pmk):  # models/utils.py:11-32 restated
-    EPS = 1e-10
-    mask1 = pmk >= 0
-    pmk1 = pmk * mask1.detach()
-    ms1 = (torch.log(math.exp(alpha) + torch.exp(-2 * pmk1 * alpha) + EPS)
-           - torch.log(torch.exp(alpha * (-2 * pmk1 + 1)) + 1 + EPS)) / (2 * alpha) + 0.5
-    mask2 = pmk < 0
-    pmk2 = pmk * mask2.detach()
-    ms2 = (torch.log(torch.exp(alpha * (2 * pmk2 + 1)) + 1 + EPS)
-           - torch.log(math.exp(alpha) + torch.exp(alpha * 2 * pmk2) + EPS)) / (2 * alpha) + 0.5
-    return ms1 * mask1 + ms2 * mask2
-
-
 def test_mask_ste_vs_torch64():
     B, T, nq, alpha = 5, 77, 28, 2.0
     g0 = torch.Generator().manual_seed(9)
@@ -315,32 +310,6 @@ def test_generate_mask_ste_public_vs_torch64():
 
 
 # ------------------------------------------------------------------ quantizer backward
-def rvq64(z, mask, g_in, v_in, b_in, g_out, v_out, b_out, cb, codes):
-    """The reference quantizer loop (models/quantize.py:42-79, 353-423) in fp64 autograd with the
-    given codes (argmin decisions fixed: the straight-through estimator only uses them as
-    indices)."""
-    nq, N, d = cb.shape
-    D = z.shape[1]
-    w_in = wn64(g_in.reshape(-1, 1), v_in).reshape(nq, d, D)
-    w_out = wn64(g_out.reshape(-1, 1), v_out).reshape(nq, D, d)
-    residual = z
-    z_q = 0
-    commit = 0
-    cbl = 0
-    for i in range(nq):
-        z_e = torch.einsum("kc,bct->bkt", w_in[i], residual) + b_in[i][None, :, None]
-        zq = cb[i][codes[:, i]].permute(0, 2, 1)                       # (B, d, T)
-        commit_i = (z_e - zq.detach()).pow(2).mean(1)
-        cbl_i = (zq - z_e.detach()).pow(2).mean(1)
-        zst = z_e + (zq - z_e).detach()
-        z_q_i = torch.einsum("cm,bmt->bct", w_out[i], zst) + b_out[i][None, :, None]
-        residual = residual - z_q_i
-        z_q = z_q + z_q_i * mask[:, i][:, None, :]
-        commit = commit + commit_i * mask[:, i].detach()
-        cbl = cbl + cbl_i * mask[:, i].detach()
-    return z_q, commit.mean(), cbl.mean()
-
-
 @pytest.mark.parametrize("nq,B,T", [(4, 2, 20), (28, 2, 33), (9, 3, 70)])
 def test_rvq_backward_vs_torch64(nq, B, T):
     D, d, N = 1024, 8, 1024

@@ -41,6 +41,7 @@ SIGNATURES = {
                                   _P, _P],
     "vrvq_pack_convt1d_weight": [_P, _I, _I, _I, _I, _P, _P],
     "vrvq_rvq_cross_prep": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "vrvq_rvq_cross_prep_precise": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
     "vrvq_rvq_frag": [_P, _I, _I, _I, _P, _P],
     "vrvq_rvq_workspace": [_I, _I, _I, _P],
     "vrvq_rvq_encode": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F,

@@ -91,7 +91,14 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 // Prep (once per weight version, like the weight-norm fold):
 //   mcol[j][i][k][m] = sum_c W_in(i)[k][c] W_out(j)[c][m] for i > j (else 0)   (this kernel)
 //   qb[i][k]         = sum_c W_in(i)[k][c] (sum_{j<i} b_out(j)[c])   (cross_prep_qb_kernel)
-// one fmaf chain over c in order per output.
+// one fmaf chain over c in order per output. Acc = float is the inference path's; Acc = double
+// (vrvq_rvq_cross_prep_precise, the training step) rounds each entry once: the entries are
+// cancelling 1024-term dots, and the fp32 chain's 1e-6 of |M| is 4 - 10 x fp32's own error in
+// the quantizer's weight gradients (DESIGN, "What the quantizer's training backward ...").
+__device__ __forceinline__ float cp_fma(float a, float b, float acc) { return fmaf(a, b, acc); }
+__device__ __forceinline__ double cp_fma(double a, double b, double acc) { return fma(a, b, acc); }
+
+template <typename Acc>
 __global__ void cross_prep_kernel(const float* __restrict__ w_in_t,  // [nq][D][8]
                                   const float* __restrict__ w_out,   // [nq][D][8]
                                   const float* __restrict__ b_out,   // [nq][D]
@@ -101,13 +108,13 @@ __global__ void cross_prep_kernel(const float* __restrict__ w_in_t,  // [nq][D][
   if (e < nm) {
     const int m = e & 7, k = (e >> 3) & 7, ij = e >> 6;
     const int i = ij % nq, j = ij / nq;
-    float acc = 0.0f;
+    Acc acc = 0;
     if (i > j) {
       const float* wi = w_in_t + (size_t)i * RD * RCD + k;
       const float* wo = w_out + (size_t)j * RD * RCD + m;
-      for (int c = 0; c < RD; ++c) acc = fmaf(wi[c * RCD], wo[c * RCD], acc);
+      for (int c = 0; c < RD; ++c) acc = cp_fma((Acc)wi[c * RCD], (Acc)wo[c * RCD], acc);
     }
-    mcol[e] = acc;
+    mcol[e] = (float)acc;
   }
 }
 
@@ -116,20 +123,21 @@ __global__ void cross_prep_kernel(const float* __restrict__ w_in_t,  // [nq][D][
 // over c in order -- the values of the earlier one-thread-per-output form, which re-summed the
 // biases for every channel in each of its nq * 8 threads (O(nq^2 D) serial work: ~1 ms per
 // weight version at nq = 28, i.e. every training step).
+template <typename Acc>
 __global__ __launch_bounds__(RD) void cross_prep_qb_kernel(const float* __restrict__ w_in_t,
                                                            const float* __restrict__ b_out,
                                                            float* __restrict__ qb) {
-  __shared__ float bs_s[RD];
+  __shared__ Acc bs_s[RD];
   const int i = blockIdx.x, c = threadIdx.x;
-  float bs = 0.0f;
+  Acc bs = 0;
   for (int j = 0; j < i; ++j) bs = bs + b_out[(size_t)j * RD + c];
   bs_s[c] = bs;
   __syncthreads();
   if (c < RCD) {
     const float* wi = w_in_t + (size_t)i * RD * RCD + c;
-    float acc = 0.0f;
-    for (int cc = 0; cc < RD; ++cc) acc = fmaf(wi[cc * RCD], bs_s[cc], acc);
-    qb[i * RCD + c] = acc;
+    Acc acc = 0;
+    for (int cc = 0; cc < RD; ++cc) acc = cp_fma((Acc)wi[cc * RCD], bs_s[cc], acc);
+    qb[i * RCD + c] = (float)acc;
   }
 }
 
@@ -1689,18 +1697,30 @@ extern "C" int vrvq_debug_set_fused_flags(int flags) {
 }
 #endif
 
-extern "C" int vrvq_rvq_cross_prep(const float* w_in_t, const float* w_out, const float* b_out,
-                                   int nq, int dim, int cdim, float* mcol, float* qb,
-                                   vrvq_stream_t stream) {
+template <typename Acc>
+static int cross_prep(const float* w_in_t, const float* w_out, const float* b_out, int nq, int dim,
+                      int cdim, float* mcol, float* qb, vrvq_stream_t stream) {
   VRVQ_CHECK_ARG(w_in_t && w_out && b_out && mcol && qb && nq > 0);
   if (dim != RD || cdim != RCD) return VRVQ_ERR_UNSUPPORTED;
   // mcol: one thread per (j, i, k, m) chain; qb: one workgroup per stage (cross_prep_qb_kernel)
   const int total = nq * nq * 64;
-  hipLaunchKernelGGL(cross_prep_kernel, dim3((total + 255) / 256), dim3(256), 0,
+  hipLaunchKernelGGL(cross_prep_kernel<Acc>, dim3((total + 255) / 256), dim3(256), 0,
                      as_stream(stream), w_in_t, w_out, b_out, nq, mcol, qb);
-  hipLaunchKernelGGL(cross_prep_qb_kernel, dim3(nq), dim3(RD), 0, as_stream(stream), w_in_t, b_out,
-                     qb);
+  hipLaunchKernelGGL(cross_prep_qb_kernel<Acc>, dim3(nq), dim3(RD), 0, as_stream(stream), w_in_t,
+                     b_out, qb);
   return vrvq_launch_status();
+}
+
+extern "C" int vrvq_rvq_cross_prep(const float* w_in_t, const float* w_out, const float* b_out,
+                                   int nq, int dim, int cdim, float* mcol, float* qb,
+                                   vrvq_stream_t stream) {
+  return cross_prep<float>(w_in_t, w_out, b_out, nq, dim, cdim, mcol, qb, stream);
+}
+
+extern "C" int vrvq_rvq_cross_prep_precise(const float* w_in_t, const float* w_out,
+                                           const float* b_out, int nq, int dim, int cdim,
+                                           float* mcol, float* qb, vrvq_stream_t stream) {
+  return cross_prep<double>(w_in_t, w_out, b_out, nq, dim, cdim, mcol, qb, stream);
 }
 
 extern "C" int vrvq_rvq_frag(const float* cbn, int nq, int ncode, int cdim, float* cbf,

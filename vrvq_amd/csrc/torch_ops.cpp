@@ -323,9 +323,10 @@ void check_rvq_weights(const Tensor& z, const Tensor& w_in_t, const Tensor& b_in
   TORCH_CHECK(b_in.numel() == nq * d && b_out.numel() == nq * D, "rvq: bias shapes");
 }
 
-// Cross terms of the projected chain (include/vrvq.h): once per weight version.
-std::tuple<Tensor, Tensor> rvq_cross_prep(const Tensor& w_in_t, const Tensor& w_out,
-                                          const Tensor& b_out) {
+// Cross terms of the projected chain (include/vrvq.h): once per weight version; precise: every
+// entry accumulated in fp64 (the training step).
+std::tuple<Tensor, Tensor> cross_prep_impl(const Tensor& w_in_t, const Tensor& w_out,
+                                           const Tensor& b_out, bool precise) {
   check_t(w_in_t, "w_in_t");
   check_on(w_out, w_in_t, "w_out");
   check_on(b_out, w_in_t, "b_out");
@@ -335,11 +336,21 @@ std::tuple<Tensor, Tensor> rvq_cross_prep(const Tensor& w_in_t, const Tensor& w_
   const int64_t nq = w_in_t.size(0), D = w_in_t.size(1), d = w_in_t.size(2);
   Tensor mcol = empty_f({nq, nq, d, d}, w_in_t);
   Tensor qb = empty_f({nq, d}, w_in_t);
-  check_rc(vrvq_rvq_cross_prep(w_in_t.data_ptr<float>(), w_out.data_ptr<float>(),
-                               b_out.data_ptr<float>(), (int)nq, (int)D, (int)d,
-                               mcol.data_ptr<float>(), qb.data_ptr<float>(), stream_of(w_in_t)),
-           "vrvq_rvq_cross_prep");
+  auto fn = precise ? vrvq_rvq_cross_prep_precise : vrvq_rvq_cross_prep;
+  check_rc(fn(w_in_t.data_ptr<float>(), w_out.data_ptr<float>(), b_out.data_ptr<float>(), (int)nq,
+              (int)D, (int)d, mcol.data_ptr<float>(), qb.data_ptr<float>(), stream_of(w_in_t)),
+           precise ? "vrvq_rvq_cross_prep_precise" : "vrvq_rvq_cross_prep");
   return {mcol, qb};
+}
+
+std::tuple<Tensor, Tensor> rvq_cross_prep(const Tensor& w_in_t, const Tensor& w_out,
+                                          const Tensor& b_out) {
+  return cross_prep_impl(w_in_t, w_out, b_out, false);
+}
+
+std::tuple<Tensor, Tensor> rvq_cross_prep_precise(const Tensor& w_in_t, const Tensor& w_out,
+                                                  const Tensor& b_out) {
+  return cross_prep_impl(w_in_t, w_out, b_out, true);
 }
 
 // The normalised codebooks in the chain's MFMA fragment order (include/vrvq.h, vrvq_rvq_frag).
@@ -1570,6 +1581,7 @@ TORCH_LIBRARY(vrvq, m) {
       "Tensor inv_alpha2, Tensor w1, Tensor b1, Tensor? alpha_out, Tensor? inv_alpha_out, "
       "bool want_raw, Tensor? w7_x3=None, Tensor? w1_x3=None) -> (Tensor, Tensor)");
   m.def("rvq_cross_prep(Tensor w_in_t, Tensor w_out, Tensor b_out) -> (Tensor, Tensor)");
+  m.def("rvq_cross_prep_precise(Tensor w_in_t, Tensor w_out, Tensor b_out) -> (Tensor, Tensor)");
   m.def("rvq_frag(Tensor cbn) -> Tensor");
   m.def(
       "rvq_encode(Tensor z, Tensor w_in_t, Tensor b_in, Tensor cb, Tensor cbf, Tensor c2, "
@@ -1678,6 +1690,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("snake_conv_transpose1d", &snake_conv_transpose1d); \
   m.impl("residual_unit", &residual_unit); \
   m.impl("rvq_cross_prep", &rvq_cross_prep); \
+  m.impl("rvq_cross_prep_precise", &rvq_cross_prep_precise); \
   m.impl("rvq_frag", &rvq_frag); \
   m.impl("rvq_encode", &rvq_encode); \
   m.impl("rvq_pack_w_in", &rvq_pack_w_in); \

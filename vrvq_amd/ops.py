@@ -201,6 +201,12 @@ def rvq_cross_prep(w_in_t, w_out, b_out):
     return _ops().rvq_cross_prep(w_in_t, w_out, b_out)
 
 
+def rvq_cross_prep_precise(w_in_t, w_out, b_out):
+    """rvq_cross_prep with every entry accumulated in fp64 and rounded once (the training step:
+    the fp32 chain's rounding of M dominates the error of the quantizer's gradients)."""
+    return _ops().rvq_cross_prep_precise(w_in_t, w_out, b_out)
+
+
 def rvq_frag(cbn):
     """The normalised codebooks in the chain's MFMA fragment order (once per weight version)."""
     return _ops().rvq_frag(cbn)
@@ -513,6 +519,11 @@ def _register_fakes():
         return pair(x, tuple(x.shape), alpha_out, want_raw)
 
     @reg("vrvq::rvq_cross_prep")
+    def _(w_in_t, w_out, b_out):
+        nq, _D, d = w_in_t.shape
+        return f32(w_in_t, (nq, nq, d, d)), f32(w_in_t, (nq, d))
+
+    @reg("vrvq::rvq_cross_prep_precise")
     def _(w_in_t, w_out, b_out):
         nq, _D, d = w_in_t.shape
         return f32(w_in_t, (nq, nq, d, d)), f32(w_in_t, (nq, d))

@@ -217,7 +217,9 @@ class _RvqTrain(torch.autograd.Function):
         cbn, c2 = ops.codebook_prep(cbd)
         cbf = ops.rvq_frag(cbn)
         b_in_d, b_out_d = b_in.detach().contiguous(), b_out.detach().contiguous()
-        mcol, qb = ops.rvq_cross_prep(w_in_t, w_out, b_out_d)
+        # M_ij and Qb accumulated in fp64: their fp32 chains' rounding (1e-6 of |M|) would be the
+        # largest error of z_e and of every gradient below
+        mcol, qb = ops.rvq_cross_prep_precise(w_in_t, w_out, b_out_d)
         codes, lat, loss_pf, zst, z_q = ops.rvq_encode_train(z, w_in_t, b_in_d, cbd, cbf, c2,
                                                              w_out, b_out_d, mcol, qb, mask)
         commit = ops.masked_loss(loss_pf, mask)
