@@ -9,7 +9,6 @@ the reference — `discriminators.<i>.convs.<j>.0.weight_g` etc. — so referenc
 from __future__ import annotations
 
 import math
-import os
 from typing import List, Sequence, Tuple
 
 import torch
@@ -37,16 +36,13 @@ def _run(layers, x, fmap: list):
 _MPD_LAYERS = [(1, 32, 3), (32, 128, 3), (128, 512, 3), (512, 1024, 3), (1024, 1024, 1)]
 
 
-# The period discriminators' (k, 1) Conv2d run as Conv1d over the folded batch (B * period, C,
-# frames): the same sums per output element (each column is an independent 1-D signal); the
-# feature maps are then laid out (B * period, C, frames), which every use of them (means and
-# elementwise L1 between real and fake, losses.GANLoss) is invariant to. VRVQ_MPD_1D=0: the
-# reference's Conv2d over (B, C, frames, period).
-MPD_1D = os.environ.get("VRVQ_MPD_1D", "1") != "0"
-# ... and as plain GEMMs (hipBLASLt fp32) over a channels-last (B * period, frames, C) layout:
-# the k-tap windows of the strided conv gathered once (unfold), no layout transposes between
-# layers (VRVQ_MPD_GEMM=0: F.conv1d, MIOpen).
-MPD_GEMM = os.environ.get("VRVQ_MPD_GEMM", "1") != "0"
+# The period discriminators' (k, 1) Conv2d run as 1-D convs over the folded batch (each column
+# is an independent 1-D signal: the same sums per output element), as plain GEMMs (hipBLASLt
+# fp32) over a channels-last (B * period, frames, C) layout: the k-tap windows of the strided conv
+# gathered once (unfold), no layout transposes between layers. The feature maps keep that layout,
+# which every use of them (means and elementwise L1 between real and fake, losses.GANLoss) is
+# invariant to. A test switch: False runs the reference's Conv2d over (B, C, frames, period).
+MPD_1D = True
 
 
 def _conv1d_cl(h: torch.Tensor, w: torch.Tensor, bias, stride: int, pad: int) -> torch.Tensor:
@@ -76,12 +72,10 @@ class MPD(nn.Module):
     def to_reference_layout(self, fmap: torch.Tensor, batch: int) -> torch.Tensor:
         """One map of forward() in the reference's (B, C, frames, period) layout (a view where
         the folded layouts allow; the values are unchanged)."""
-        if fmap.dim() == 4:  # already the Conv2d form (VRVQ_MPD_1D=0)
+        if fmap.dim() == 4:  # already the Conv2d form (MPD_1D off)
             return fmap
-        p = self.period
-        if MPD_GEMM:  # (B * p, frames, C)
-            return fmap.reshape(batch, p, fmap.shape[1], fmap.shape[2]).permute(0, 3, 2, 1)
-        return fmap.reshape(batch, p, fmap.shape[1], fmap.shape[2]).permute(0, 2, 3, 1)
+        # (B * period, frames, C)
+        return fmap.reshape(batch, self.period, fmap.shape[1], fmap.shape[2]).permute(0, 3, 2, 1)
 
     def forward(self, x):
         t = x.shape[-1]
@@ -90,17 +84,13 @@ class MPD(nn.Module):
         x = x.reshape(b, c, n // self.period, self.period)
         fmap: list = []
         if MPD_1D:
-            # (B, C, frames, period) -> (B * period, C, frames) or channels-last (.., frames, C)
+            # (B, C, frames, period) -> channels-last (B * period, frames, C)
             h = x.permute(0, 3, 1, 2).reshape(b * self.period, c, n // self.period)
-            if MPD_GEMM:
-                h = h.transpose(1, 2)
+            h = h.transpose(1, 2)
             for layer in list(self.convs) + [self.conv_post]:
                 conv = layer[0] if isinstance(layer, nn.Sequential) else layer
                 w = torch._weight_norm(conv.weight_v, conv.weight_g, 0)[..., 0]
-                if MPD_GEMM:
-                    h = _conv1d_cl(h, w, conv.bias, conv.stride[0], conv.padding[0])
-                else:
-                    h = F.conv1d(h, w, conv.bias, stride=conv.stride[0], padding=conv.padding[0])
+                h = _conv1d_cl(h, w, conv.bias, conv.stride[0], conv.padding[0])
                 if layer is not self.conv_post:
                     h = F.leaky_relu(h, 0.1)
                 fmap.append(h)
@@ -200,13 +190,12 @@ class Discriminator(nn.Module):
     (models/discriminator.py:178-220). forward(x) -> list (per discriminator) of feature maps,
     the last one the logits.
 
-    Feature-map layout: with VRVQ_MPD_1D / VRVQ_MPD_GEMM on (the default) each
-    period discriminator's maps are (B * period, frames, C) -- the channels-last folded batch its
+    Feature-map layout: each period discriminator's maps are (B * period, frames, C) -- the channels-last folded batch its
     GEMMs run on -- where the reference returns (B, C, frames, period). The values are the same
     and every consumer in the training step (means, elementwise L1 between the real and the fake
     maps: losses.GANLoss) is layout-invariant; a consumer that indexes the maps (hooks, per-layer
-    comparisons against reference fixtures) takes MPD.to_reference_layout(map, B) or runs with
-    VRVQ_MPD_1D=0 (the reference's Conv2d layout). MSD / MRD maps keep the reference layout."""
+    comparisons against reference fixtures) takes MPD.to_reference_layout(map, B). MSD / MRD maps
+    keep the reference layout."""
 
     def __init__(self, rates: List[int] = [], periods: List[int] = [2, 3, 5, 7, 11],
                  fft_sizes: List[int] = [2048, 1024, 512], sample_rate: int = 44100,

@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, paths
 
 
 def _param_key(*ps):
@@ -56,7 +56,37 @@ def _wn_init(weight_v: torch.Tensor, fan_in: int, out_dim0: int):
     return g
 
 
-class WNConv1d(nn.Module):
+class _WNConv(nn.Module):
+    """What the two weight-normalised convs share: the fold, and one packed record of the folded
+    weight (ops.PackedConv) per parameter version and setting of the ops.X3 switch."""
+
+    kind = "conv"  # paths.x3_planes / ops.pack_conv
+    _cache = None
+
+    def folded_weight(self) -> torch.Tensor:
+        """w = v * (g / ||v||) in the reference layout."""
+        return ops.weight_norm(self.weight_g.detach().contiguous(), self.weight_v.detach().contiguous())
+
+    def packed(self) -> ops.PackedConv:
+        key = (_param_key(self.weight_g, self.weight_v), ops.X3)
+        if self._cache is None or self._cache[0] != key:
+            k, s = self.kernel_size[0], self.stride[0]
+            planes = ops.X3 and paths.x3_planes(self.kind, self.in_channels, k, s)
+            self._cache = (key, ops.pack_conv(self.folded_weight(), self.kind, s, planes))
+        return self._cache[1]
+
+    def prepared(self):
+        """(packed weight, its padded output rows)."""
+        p = self.packed()
+        return p.wp, p.cout_pad
+
+    def prepared_x3(self):
+        """bf16 planes of the packed weight for the x3 MFMA path, or None (fp32-input MFMA path):
+        paths.x3_planes says which convs have them."""
+        return self.packed().w_x3
+
+
+class WNConv1d(_WNConv):
     """Weight-normalised Conv1d (models/layers.py:17-18), fused Snake prologue."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int, stride: int = 1,
@@ -74,55 +104,22 @@ class WNConv1d(nn.Module):
         g = _wn_init(v, in_channels * kernel_size, out_channels)
         self.weight_g = nn.Parameter(g.reshape(out_channels, 1, 1).clone())
         self.weight_v = nn.Parameter(v)
-        self._cache = None
-        self._cache_x3 = None
-
-    def folded_weight(self) -> torch.Tensor:
-        """w = v * (g / ||v||) in the reference layout (Cout, Cin, k)."""
-        return ops.weight_norm(self.weight_g.detach().contiguous(), self.weight_v.detach().contiguous())
-
-    def prepared(self):
-        key = _param_key(self.weight_g, self.weight_v)
-        if self._cache is None or self._cache[0] != key:
-            wp, cout_pad = ops.pack_conv1d_weight(self.folded_weight())
-            self._cache = (key, wp, cout_pad)
-        return self._cache[1], self._cache[2]
-
-    def prepared_x3(self):
-        """bf16 planes of the packed weight for the x3 MFMA path, or None (fp32-input MFMA
-        path): stride-1 k in {1, 3, 7} with >= 8 input channels, and the strided encoder convs
-        (k = 2s, s a power of two) as a stride-1 k = 2 conv over the phase-split view of x,
-        whose weight is W'[co][c*s + r][j] = W[co][c][j*s + r] (include/vrvq.h vrvq_conv1d)."""
-        k, s = self.kernel_size[0], self.stride[0]
-        if not ops.X3 or self.in_channels < 8:
-            return None
-        strided = (s > 1 and k == 2 * s and s & (s - 1) == 0 and ops.X3_STRIDED)
-        if not ((s == 1 and k in ops.X3_TAPS) or strided):
-            return None
-        key = _param_key(self.weight_g, self.weight_v)
-        if self._cache_x3 is None or self._cache_x3[0] != key:
-            if strided:
-                self._cache_x3 = (key, ops.pack_x3_strided_weight(self.folded_weight(), s))
-            else:
-                wp, _ = self.prepared()
-                self._cache_x3 = (key, ops.pack_x3_weight(wp, k))
-        return self._cache_x3[1]
 
     def forward(self, x: torch.Tensor, snake: Optional[Snake1d] = None,
                 residual: Optional[torch.Tensor] = None, epilogue: int = ops.EPI_NONE,
                 out_snake: Optional[Snake1d] = None, want_raw: bool = True):
         """conv(snake(x)) (+ residual, epilogue). With out_snake (the consumer's Snake1d)
         returns (y or None, out_snake(y)) computed in the same epilogue."""
-        wp, cout_pad = self.prepared()
+        p = self.packed()
         alpha = inv = None
         if snake is not None:
             alpha, inv = snake.prepared()
-        return ops.conv1d(x, wp, self.out_channels, cout_pad, self.kernel_size[0],
+        return ops.conv1d(x, p.wp, self.out_channels, p.cout_pad, self.kernel_size[0],
                           self.stride[0], self.padding[0], self.dilation[0],
                           bias=self.bias.detach(), alpha=alpha, inv_alpha=inv,
                           residual=residual, epilogue=epilogue,
                           out_snake=None if out_snake is None else out_snake.prepared(),
-                          want_raw=want_raw, w_x3=self.prepared_x3())
+                          want_raw=want_raw, w_x3=p.w_x3)
 
     def forward_proj(self, x: torch.Tensor, w3in: torch.Tensor, nq: int,
                      snake: Optional[Snake1d] = None, want_z: bool = False):
@@ -131,18 +128,19 @@ class WNConv1d(nn.Module):
         (8, B*T, 8 nq) channel-split projection partials rvq_encode_part takes."""
         if self.stride[0] != 1:
             raise RuntimeError("forward_proj: stride-1 convs only")
-        wp, _ = self.prepared()
+        p = self.packed()
         alpha = inv = None
         if snake is not None:
             alpha, inv = snake.prepared()
-        return ops.conv1d_proj(x, wp, self.out_channels, self.kernel_size[0], w3in, nq,
+        return ops.conv1d_proj(x, p.wp, self.out_channels, self.kernel_size[0], w3in, nq,
                                self.padding[0], self.dilation[0], bias=self.bias.detach(),
-                               alpha=alpha, inv_alpha=inv, w_x3=self.prepared_x3(),
-                               want_z=want_z)
+                               alpha=alpha, inv_alpha=inv, w_x3=p.w_x3, want_z=want_z)
 
 
-class WNConvTranspose1d(nn.Module):
+class WNConvTranspose1d(_WNConv):
     """Weight-normalised ConvTranspose1d (models/layers.py:21-22); norm over dim 0 = Cin."""
+
+    kind = "convt"
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int, stride: int = 1,
                  padding: int = 0):
@@ -160,46 +158,21 @@ class WNConvTranspose1d(nn.Module):
         g = _wn_init(v, out_channels * kernel_size, in_channels)
         self.weight_g = nn.Parameter(g.reshape(in_channels, 1, 1).clone())
         self.weight_v = nn.Parameter(v)
-        self._cache = None
-        self._cache_x3 = None
-
-    def folded_weight(self) -> torch.Tensor:
-        return ops.weight_norm(self.weight_g.detach().contiguous(), self.weight_v.detach().contiguous())
-
-    def prepared(self):
-        key = _param_key(self.weight_g, self.weight_v)
-        if self._cache is None or self._cache[0] != key:
-            wp, cout_pad = ops.pack_convt1d_weight(self.folded_weight(), self.stride[0])
-            self._cache = (key, wp, cout_pad)
-        return self._cache[1], self._cache[2]
-
-    def prepared_x3(self):
-        """bf16 planes of the polyphase weight (2 taps) for the x3 MFMA path, or None."""
-        if not (ops.X3 and self.in_channels >= 8):
-            return None
-        wp, _ = self.prepared()
-        key = _param_key(self.weight_g, self.weight_v)
-        if self._cache_x3 is None or self._cache_x3[0] != key:
-            self._cache_x3 = (key, ops.pack_x3_weight(wp, 2))
-        return self._cache_x3[1]
 
     def forward(self, x: torch.Tensor, snake: Optional[Snake1d] = None,
                 out_snake: Optional[Snake1d] = None, want_raw: bool = True):
-        wp, cout_pad = self.prepared()
+        p = self.packed()
         alpha = inv = None
         if snake is not None:
             alpha, inv = snake.prepared()
-        return ops.conv_transpose1d(x, wp, self.out_channels, cout_pad, self.stride[0],
+        return ops.conv_transpose1d(x, p.wp, self.out_channels, p.cout_pad, self.stride[0],
                                     bias=self.bias.detach(), alpha=alpha, inv_alpha=inv,
                                     out_snake=None if out_snake is None else out_snake.prepared(),
-                                    want_raw=want_raw, pad=self.padding[0],
-                                    w_x3=self.prepared_x3())
+                                    want_raw=want_raw, pad=self.padding[0], w_x3=p.w_x3)
 
 
 class ResidualUnit(nn.Module):
     """x + conv1(snake(conv7_dil(snake(x))))  (models/layers.py:52-68)."""
-
-    fused = True  # class-level switch (tests / A-B timing): single-launch form where supported
 
     def __init__(self, dim: int = 16, dilation: int = 1):
         super().__init__()
@@ -221,33 +194,24 @@ class ResidualUnit(nn.Module):
         return self.block[3](y, snake=self.block[2], residual=x)
 
     def runs_fused(self) -> bool:
-        C = self.block[1].in_channels
-        return self.fused and C in ops.RU_FUSED_CHANNELS and not (C == 256 and ops.X3 and
-                                                                 ops.RU256_SPLIT)
+        return paths.ru_fused(self.block[1].in_channels, ops.X3)
 
     def run(self, x: torch.Tensor, x_snk: torch.Tensor, out_snake: Snake1d, want_raw: bool):
         """Chained form: x_snk = block[0](x) was produced by the previous layer's epilogue.
-        For C in ops.RU_FUSED_CHANNELS one launch (vrvq_residual_unit: block[2](h) stays in
-        LDS); otherwise the k7 conv writes only block[2](h) (h has no other consumer) and the
-        k1 conv adds the skip. Either way the output is (y if want_raw, out_snake(y)) (bit for
-        bit the same where both forms run the k7 with the same K chunking; the two-launch k7 on
-        the 64 x 256 pair tiles -- M >= 128, T >= 640 -- sums in another order). The default
-        fused set is C = 64 / 96 / 128 (and C = 256 without the x3 weights): C = 192 runs as two
-        launches since the 192-row x3 k1 tiles (+2.8 % end to end,
-        profiles/r04z_ru_fusion_ab.txt)."""
-        # C = 256 with the x3 weights: the two launches (k7 on the x3 path at 128-row tiles,
-        # then k1 + skip) beat the fused kernel, whose 256-row x3 weight stage does not fit
-        # twice per CU and therefore keeps the fp32 MFMA (profiles/r02zi_bench_ab.txt)
+        Where paths.ru_fused says so (C = 64 / 96 / 128, and C = 256 only without the x3 planes)
+        one launch (vrvq_residual_unit: block[2](h) stays in LDS); otherwise the k7 conv writes
+        only block[2](h) (h has no other consumer) and the k1 conv adds the skip. Either way the
+        output is (y if want_raw, out_snake(y)) (bit for bit the same where both forms run the k7
+        with the same K chunking; the two-launch k7 on the 64 x 256 pair tiles -- M >= 128,
+        T >= 640 -- sums in another order)."""
         if self.runs_fused():
-            w7, cp7 = self.block[1].prepared()
-            w1, cp1 = self.block[3].prepared()
+            p7, p1 = self.block[1].packed(), self.block[3].packed()
             a2, ia2 = self.block[2].prepared()
-            return ops.residual_unit(x, x_snk, self.block[1].dilation[0], w7,
-                                     self.block[1].bias.detach(), a2, ia2, w1,
-                                     self.block[3].bias.detach(), cp7,
+            return ops.residual_unit(x, x_snk, self.block[1].dilation[0], p7.wp,
+                                     self.block[1].bias.detach(), a2, ia2, p1.wp,
+                                     self.block[3].bias.detach(), p7.cout_pad,
                                      out_snake=out_snake.prepared(), want_raw=want_raw,
-                                     w7_x3=self.block[1].prepared_x3(),
-                                     w1_x3=self.block[3].prepared_x3())
+                                     w7_x3=p7.w_x3, w1_x3=p1.w_x3)
         return self.run_two_launch(x, x_snk, out_snake, want_raw)
 
     def run_two_launch(self, x, x_snk, out_snake: Snake1d, want_raw: bool):

@@ -8,7 +8,6 @@ libvrvq_hip.so (see ops.py); the modules here hold parameters and orchestrate la
 from __future__ import annotations
 
 import math
-import os
 from typing import List, Optional, Union
 
 import numpy as np
@@ -165,8 +164,8 @@ class VectorQuantize(nn.Module):
 # The eval encode hands z to the quantizer as its stage projections: the encoder's last conv
 # computes every stage's in_proj in its epilogue (vrvq_conv1d_proj) and the quantizer runs from
 # those partials (vrvq_rvq_encode_part: no z read, no projection in front of the chain).
-# VRVQ_RVQ_PROJ=0 (A/B): z (B, D, T) and vrvq_rvq_encode.
-RVQ_PROJ = os.environ.get("VRVQ_RVQ_PROJ", "1") != "0"
+# A test switch: False hands over z (B, D, T) and runs vrvq_rvq_encode (tests flip it).
+RVQ_PROJ = True
 
 
 class ProjectedZ:

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 import threading
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -145,16 +145,9 @@ def conv_transpose1d(x: torch.Tensor, w_packed: torch.Tensor, cout: int, cout_pa
     return _none(y) if out_snake is None else (_none(y), ys)
 
 
-RU_FUSED_CHANNELS = tuple(int(c) for c in os.environ.get("VRVQ_RU_FUSED", "64,96,128,256").split(",") if c)
-
-# The bf16x3 split MFMA path (include/vrvq.h, csrc/conv_x3.h) for the stride-1 convs of the
-# inference path; VRVQ_CONV_X3=0 keeps every conv on the fp32-input MFMA (A/B and tests).
-X3 = os.environ.get("VRVQ_CONV_X3", "1") != "0"
-X3_TAPS = (1, 2, 3, 7)
-RU256_SPLIT = os.environ.get("VRVQ_RU256_SPLIT", "1") != "0"
-# The strided encoder convs (k = 2s) on the x3 path through the phase-split view (vrvq_conv1d);
-# VRVQ_CONV_X3_STRIDED=0 keeps them on the fp32-input MFMA's strided window (A/B).
-X3_STRIDED = os.environ.get("VRVQ_CONV_X3_STRIDED", "1") != "0"
+# The bf16x3 split MFMA path (include/vrvq.h, csrc/conv_x3.h) for the convs paths.x3_planes names.
+# A test switch: False keeps every conv on the fp32-input MFMA (tests flip it; nothing else does).
+X3 = True
 
 
 def x3_size(cin: int, k: int, cout_pad: int) -> int:
@@ -180,6 +173,32 @@ def pack_x3_strided_weight(w: torch.Tensor, stride: int) -> torch.Tensor:
     wv = w.reshape(co, ci, 2, s).permute(0, 1, 3, 2).reshape(co, ci * s, 2).contiguous()
     wp, _ = pack_conv1d_weight(wv)
     return pack_x3_weight(wp, 2)
+
+
+class PackedConv(NamedTuple):
+    """What a conv launch takes of its weight: the packed fp32 array, its padded output rows and
+    the bf16x3 planes (None: the fp32-input MFMA path)."""
+    wp: torch.Tensor
+    cout_pad: int
+    w_x3: Optional[torch.Tensor]
+
+
+def pack_conv(w: torch.Tensor, kind: str, stride: int = 1, planes: bool = False) -> PackedConv:
+    """A folded weight as its launch takes it. kind "conv": w (Cout, Cin, k) for conv1d, the
+    planes those of the phase-split weight when stride > 1 (pack_x3_strided_weight); "convt": w
+    (Cin, Cout, 2 stride) for conv_transpose1d, two taps per phase; "flip": w (Cout, Cin, k) of a
+    stride-1 Conv1d as its adjoint's weight, a stride-1 conv from Cout to Cin channels."""
+    if kind == "convt":
+        wp, cout_pad = pack_convt1d_weight(w, stride)
+        taps = 2
+    else:
+        wp, cout_pad = pack_conv1d_flip(w) if kind == "flip" else pack_conv1d_weight(w)
+        taps = w.shape[2]
+    if not planes:
+        return PackedConv(wp, cout_pad, None)
+    if kind == "conv" and stride > 1:
+        return PackedConv(wp, cout_pad, pack_x3_strided_weight(w, stride))
+    return PackedConv(wp, cout_pad, pack_x3_weight(wp, taps))
 
 
 def residual_unit(x, x_snk, dil: int, w7, b7, alpha2, inv_alpha2, w1, b1, cout_pad: int,

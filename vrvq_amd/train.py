@@ -24,28 +24,19 @@ reference's order, so a seeded step draws bit-identical values.
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
 
-from . import ops
-
-# Forward and adjoint convs of the training step on the bf16x3 split MFMA path (csrc/conv_x3.h:
-# fp32-accurate; the weights change every step, so their split planes are packed per call).
-# VRVQ_TRAIN_X3=0 keeps them on the fp32-input MFMA (A/B).
-TRAIN_X3 = ops.X3 and os.environ.get("VRVQ_TRAIN_X3", "1") != "0"
+from . import ops, paths
 
 
-def _x3(wp: torch.Tensor, k: int) -> Optional[torch.Tensor]:
-    """Split planes of a packed weight for a stride-1 conv (k taps) or a polyphase ConvT (k=2)."""
-    return ops.pack_x3_weight(wp, k) if TRAIN_X3 and k in ops.X3_TAPS else None
-
-
-def _x3s(w: torch.Tensor, k: int, stride: int) -> Optional[torch.Tensor]:
-    """Split planes of a strided conv's phase-split weight (k = 2s, s a power of two)."""
-    ok = TRAIN_X3 and ops.X3_STRIDED and k == 2 * stride and stride & (stride - 1) == 0
-    return ops.pack_x3_strided_weight(w, stride) if ok and w.shape[1] >= 8 else None
+def _pack(w: torch.Tensor, kind: str, cin: int, k: int, stride: int) -> ops.PackedConv:
+    """A folded weight as a forward or adjoint conv of the step takes it (ops.pack_conv kinds; a
+    "flip" runs as a conv), with bf16x3 planes where paths.x3_planes gives them to a conv of cin
+    input channels (fp32-accurate; the weights change every step, so this runs per call)."""
+    planes = ops.X3 and paths.x3_planes("convt" if kind == "convt" else "conv", cin, k, stride)
+    return ops.pack_conv(w, kind, stride, planes)
 
 
 def _c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -64,15 +55,15 @@ class _SnakeConv(torch.autograd.Function):
         inv = ops.snake_inv_alpha(alpha.detach()) if alpha is not None else None
         a = alpha.detach() if alpha is not None else None
         b = bias.detach()
+        p = _pack(w, kind, x.shape[1], k, stride)
         if kind == "conv":
-            wp, cp = ops.pack_conv1d_weight(w)
-            y = ops.conv1d(x, wp, cout, cp, k, stride, pad, dil, bias=b, alpha=a, inv_alpha=inv,
+            y = ops.conv1d(x, p.wp, cout, p.cout_pad, k, stride, pad, dil, bias=b, alpha=a,
+                           inv_alpha=inv,
                            residual=_c(residual.detach()) if residual is not None else None,
-                           epilogue=epi, w_x3=_x3(wp, k) if stride == 1 else _x3s(w, k, stride))
+                           epilogue=epi, w_x3=p.w_x3)
         else:
-            wp, cp = ops.pack_convt1d_weight(w, stride)
-            y = ops.conv_transpose1d(x, wp, cout, cp, stride, bias=b, alpha=a, inv_alpha=inv,
-                                     w_x3=_x3(wp, 2))
+            y = ops.conv_transpose1d(x, p.wp, cout, p.cout_pad, stride, bias=b, alpha=a,
+                                     inv_alpha=inv, w_x3=p.w_x3)
         ctx.spec = spec
         ctx.has_alpha = alpha is not None
         ctx.has_res = residual is not None
@@ -99,16 +90,17 @@ class _SnakeConv(torch.autograd.Function):
             dg, dv = ops.weight_norm_backward(g.contiguous(), v.contiguous(), dw)
         dx = dalpha = None
         if need_x or need_a:
-            cin = x.shape[1]
+            cin = x.shape[1]  # the adjoint runs from the forward's cout channels to its cin
             if kind == "conv" and stride == 1:
-                wf, cpf = ops.pack_conv1d_flip(w)
-                dxs = ops.conv1d(gy, wf, cin, cpf, k, 1, dil * (k - 1) - pad, dil, w_x3=_x3(wf, k))
+                p = _pack(w, "flip", cout, k, 1)
+                dxs = ops.conv1d(gy, p.wp, cin, p.cout_pad, k, 1, dil * (k - 1) - pad, dil,
+                                 w_x3=p.w_x3)
             elif kind == "conv":  # strided conv: adjoint is the polyphase ConvTranspose1d
-                wt, cpt = ops.pack_convt1d_weight(w, stride)
-                dxs = ops.conv_transpose1d(gy, wt, cin, cpt, stride, w_x3=_x3(wt, 2))
+                p = _pack(w, "convt", cout, k, stride)
+                dxs = ops.conv_transpose1d(gy, p.wp, cin, p.cout_pad, stride, w_x3=p.w_x3)
             else:  # ConvTranspose1d: adjoint is the strided conv with the same weight array
-                wc, cpc = ops.pack_conv1d_weight(w)
-                dxs = ops.conv1d(gy, wc, cin, cpc, k, stride, pad, 1, w_x3=_x3s(w, k, stride))
+                p = _pack(w, "conv", cout, k, stride)
+                dxs = ops.conv1d(gy, p.wp, cin, p.cout_pad, k, stride, pad, 1, w_x3=p.w_x3)
             if dxs.shape != x.shape:
                 raise RuntimeError(f"adjoint conv shape {tuple(dxs.shape)} != {tuple(x.shape)}")
             if ctx.has_alpha:
