@@ -558,6 +558,47 @@ int vrvq_signal_metrics(const float* est, const float* ref, int rows, int ref_ro
                         double* moments, void* workspace, long long workspace_bytes,
                         vrvq_stream_t stream);
 
+/* BSS SDR (library version 112; models/utils.py:91-143 cal_metrics' "SDR",
+ * torchmetrics.functional.signal_distortion_ratio without use_cg_iter), per row and without a
+ * host sync: the estimate is projected onto the span of the filter_length delayed copies of the
+ * reference, and the ratio is the energy inside that span over the energy outside it.
+ *
+ * est [rows][samples], ref [ref_rows][samples], rows % ref_rows == 0, lengths [ref_rows] (int64,
+ * device) or NULL: rows pair up and lengths count as in vrvq_signal_metrics. For one row, p = est
+ * and t = ref over its first n samples, F = filter_length, everything in fp64:
+ *   zero_mean != 0: p and t each lose their own mean over the n samples;
+ *   t <- t / max(|t|_2, 1e-6), p <- p / max(|p|_2, 1e-6);
+ *   r[l] = sum_{i=0}^{n-1-l} t[i] t[i+l], b[l] = sum_{i=0}^{n-1-l} t[i] p[i+l], l < F (a lag
+ *   l >= n is an empty sum, 0: what torchmetrics' FFT of length 2^ceil(log2(2n-1)) gives
+ *   whenever that length is at least F);
+ *   load_diag not NaN: r[0] += load_diag;
+ *   R s = b with R[i][j] = r[|i-j|]; coh = b . s; out[row] = 10 log10(coh / (1 - coh)).
+ * n = 0, sum t^2 = 0 or sum p^2 = 0 gives NaN; a NaN in a row's data gives NaN in that row (in
+ * a reference's data: in the rows of that reference) and in no other. R is solved by
+ * Levinson-Durbin, F - 1 steps whatever the data; if a step's prediction error is not positive
+ * and finite (a singular R), the rows of that reference are NaN. coh >= 1 gives what IEEE
+ * arithmetic gives (+inf or NaN): no clamp.
+ *
+ * Three launches on `stream`, four with zero_mean (the means first); no atomics, graph-capturable.
+ * Workgroups of a fixed VRVQ_SDR_CHUNK samples store the chunk's F partial sums of b and its
+ * sums of p^2 and t p to the workspace; r and sum t^2 are formed once per reference row, not once per
+ * estimate. One workgroup per row adds the chunks in a fixed order and divides by the clamped
+ * norms. One wave per (reference row, four estimates) runs the recursion; the estimates of a wave
+ * share its prediction polynomial and each keeps its own solution. A row's bits do not depend on
+ * the other rows, on how many estimates share its reference, or on the row's address.
+ * VRVQ_ERR_ARG before any launch: null pointers, rows outside [1, 65535], ref_rows <= 0 or
+ * rows % ref_rows != 0, samples outside [1, 2^32], filter_length outside [1, 512], a workspace
+ * too small or not 8-byte aligned.
+ *   vrvq_bss_sdr_workspace  *bytes = 8 * (rows + ref_rows) * (1 + ceil(samples / VRVQ_SDR_CHUNK)
+ *                           * (filter_length + 2) + filter_length)
+ *   vrvq_bss_sdr            out [rows] fp64; load_diag NaN for none */
+#define VRVQ_SDR_CHUNK 2048
+int vrvq_bss_sdr_workspace(int rows, int ref_rows, long long samples, int filter_length,
+                           long long* bytes);
+int vrvq_bss_sdr(const float* est, const float* ref, int rows, int ref_rows, long long samples,
+                 const long long* lengths, int filter_length, int zero_mean, double load_diag,
+                 double* out, void* workspace, long long workspace_bytes, vrvq_stream_t stream);
+
 /* Spectral distance (models/loss.py:168-401 MultiScaleSTFTLoss / MelSpectrogramLoss, levels=None),
  * per row and per scale and without a host sync; no spectrogram reaches memory.
  *

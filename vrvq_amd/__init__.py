@@ -8,7 +8,7 @@ from .model import (DAC_VRVQ, Decoder, Encoder, ImportanceSubnet, ResidualVector
                     VBRResidualVectorQuantize, VectorQuantize)
 from .layers import (DecoderBlock, EncoderBlock, ResidualUnit, Snake1d, WNConv1d,
                      WNConvTranspose1d)
-from .utils import (cal_bpf_from_mask, cal_bpf_tensor, check_errors, generate_mask_hard,
+from .utils import (bss_sdr, cal_bpf_from_mask, cal_bpf_tensor, check_errors, generate_mask_hard,
                     generate_mask_ste, kbps_to_budget, level_sweep, masked_sum, rate_curve,
                     mel_distance, rd_sweep, scale_importance, signal_metrics, solve_levels,
                     solve_levels_capped, solve_quality, spectral_distance, stft_distance)
@@ -26,7 +26,7 @@ __all__ = [
     "masked_sum", "scale_importance", "level_sweep", "load_config", "model_kwargs",
     "from_config", "check_errors", "rate_curve", "solve_levels", "kbps_to_budget",
     "solve_levels_capped",
-    "signal_metrics", "rd_sweep", "solve_quality", "spectral_distance", "mel_distance",
+    "signal_metrics", "bss_sdr", "rd_sweep", "solve_quality", "spectral_distance", "mel_distance",
     "stft_distance", "resample", "loudness", "normalize_loudness",
     "Bitstream", "DACFile", "VRVQFile", "pack_bitstream", "unpack_bitstream", "pack_codes",
     "unpack_codes",

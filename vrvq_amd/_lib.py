@@ -71,6 +71,9 @@ SIGNATURES = {
     "vrvq_signal_metrics_workspace": [_I, ctypes.c_longlong, _P],
     "vrvq_signal_metrics": [_P, _P, _I, _I, ctypes.c_longlong, _P, _P, _P, _P, ctypes.c_longlong,
                             _P],
+    "vrvq_bss_sdr_workspace": [_I, _I, ctypes.c_longlong, _I, _P],
+    "vrvq_bss_sdr": [_P, _P, _I, _I, ctypes.c_longlong, _P, _I, _I, ctypes.c_double, _P, _P,
+                     ctypes.c_longlong, _P],
     "vrvq_spectral_distance_workspace": [_I, ctypes.c_longlong, _I, _P, _P],
     "vrvq_spectral_distance": [_P, _P, _I, _I, ctypes.c_longlong, _P, _I, _P, _P, _P, _P, _P,
                                ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
@@ -128,6 +131,8 @@ EXTRA = {"vrvq_status_string": ([_I], ctypes.c_char_p), "vrvq_version": ([], _I)
          "vrvq_bitstream_chunk_frames": ([], _I)}
 
 METRICS_CHUNK = 16384  # VRVQ_METRICS_CHUNK of include/vrvq.h (tests/test_metrics.py compares)
+SDR_CHUNK = 2048  # VRVQ_SDR_CHUNK (tests/test_sdr.py compares)
+SDR_MAX_FILTER = 512  # filter_length's upper bound in vrvq_bss_sdr
 SPECTRAL_TILE_SAMPLES = 8192  # VRVQ_SPECTRAL_TILE_SAMPLES (tests/test_spectral.py compares)
 RESAMPLE_TILE = 512  # VRVQ_RESAMPLE_TILE (tests/test_resample.py compares)
 LOUDNESS_CHUNK = 256  # VRVQ_LOUDNESS_CHUNK (tests/test_loudness.py compares)

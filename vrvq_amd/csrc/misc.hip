@@ -255,7 +255,7 @@ extern "C" const char* vrvq_status_string(int status) {
   }
 }
 
-extern "C" int vrvq_version(void) { return 111; }  // 101: rate control (rate.hip); 102: metrics.hip; 103: spectral.hip; 104: vrvq_conv_plan; 105: vrvq_rvq_plan, one RVQ projection (its variant switch removed); 106: resample.hip; 107: vrvq_rvq_encode = projection + rvq_pt_kernel (r04 fused kernel retired); 108: loudness.hip (BS.1770-4 integrated loudness, vrvq_loudness_plan / vrvq_loudness); 109: vrvq_spectral_distance_grad (the spectral distance's gradient, spectral.hip); 110: bitstream.hip (vrvq_bitpack_* / vrvq_bitunpack_*, the bit-granular VBR stream); 111: vrvq_rate_solve_capped / vrvq_scale_imp_packets (a per-packet rate cap, rate.hip)
+extern "C" int vrvq_version(void) { return 112; }  // 101: rate control (rate.hip); 102: metrics.hip; 103: spectral.hip; 104: vrvq_conv_plan; 105: vrvq_rvq_plan, one RVQ projection (its variant switch removed); 106: resample.hip; 107: vrvq_rvq_encode = projection + rvq_pt_kernel (r04 fused kernel retired); 108: loudness.hip (BS.1770-4 integrated loudness, vrvq_loudness_plan / vrvq_loudness); 109: vrvq_spectral_distance_grad (the spectral distance's gradient, spectral.hip); 110: bitstream.hip (vrvq_bitpack_* / vrvq_bitunpack_*, the bit-granular VBR stream); 111: vrvq_rate_solve_capped / vrvq_scale_imp_packets (a per-packet rate cap, rate.hip); 112: sdr.hip (vrvq_bss_sdr, the BSS-eval SDR)
 
 extern "C" int vrvq_weight_norm(const float* g, const float* v, int rows, int cols, float* w,
                                 vrvq_stream_t stream) {

@@ -19,6 +19,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <limits>
 #include <vector>
 
 #include "../../include/vrvq.h"
@@ -854,6 +855,47 @@ std::tuple<Tensor, Tensor> signal_metrics(const Tensor& est, const Tensor& ref,
   return {metrics, moments};
 }
 
+// --------------------------------------------------------------------------- BSS SDR
+// torchmetrics' signal_distortion_ratio of every row of est against row r % B of ref
+// (include/vrvq.h "BSS SDR"). est (R, T) or (R, 1, T), ref (B, T) or (B, 1, T), lengths (B,)
+// int64 or None, load_diag None for none -> (R,) fp64. The workspace is a tensor of the caching
+// allocator, so the call can be captured.
+Tensor bss_sdr(const Tensor& est, const Tensor& ref, const optional<Tensor>& lengths,
+               int64_t filter_length, bool zero_mean, optional<double> load_diag) {
+  check_t(est, "est");
+  check_on(ref, est, "ref");
+  TORCH_CHECK(est.dim() >= 2 && est.numel() > 0 && est.numel() == est.size(0) * est.size(-1),
+              "bss_sdr: est must be (R, T) or (R, 1, T)");
+  TORCH_CHECK(ref.dim() >= 2 && ref.numel() > 0 && ref.numel() == ref.size(0) * ref.size(-1),
+              "bss_sdr: ref must be (B, T) or (B, 1, T)");
+  const int64_t R = est.size(0), B = ref.size(0), T = est.size(-1);
+  TORCH_CHECK(ref.size(-1) == T, "bss_sdr: est has ", T, " samples, ref ", ref.size(-1));
+  TORCH_CHECK(R % B == 0, "bss_sdr: ", R, " rows are no multiple of ", B, " reference rows");
+  TORCH_CHECK(R < (1LL << 31), "bss_sdr: est too large");
+  TORCH_CHECK(filter_length >= 1 && filter_length <= 512, "bss_sdr: filter_length ",
+              filter_length, " is outside [1, 512]");
+  if (lengths.has_value()) {
+    check_on(*lengths, est, "lengths", at::kLong);
+    TORCH_CHECK(lengths->dim() == 1 && lengths->numel() == B,
+                "bss_sdr: one length per reference row");
+  }
+  c10::DeviceGuard guard(est.device());
+  long long ws_bytes = 0;
+  check_rc(vrvq_bss_sdr_workspace((int)R, (int)B, T, (int)filter_length, &ws_bytes),
+           "vrvq_bss_sdr_workspace");
+  Tensor out = at::empty({R}, est.options().dtype(at::kDouble));
+  Tensor ws = at::empty({ws_bytes / 8}, est.options().dtype(at::kDouble));
+  check_rc(vrvq_bss_sdr(
+               est.data_ptr<float>(), ref.data_ptr<float>(), (int)R, (int)B, T,
+               lengths.has_value() ? reinterpret_cast<const long long*>(lengths->data_ptr<int64_t>())
+                                   : nullptr,
+               (int)filter_length, zero_mean ? 1 : 0,
+               load_diag.has_value() ? *load_diag : std::numeric_limits<double>::quiet_NaN(),
+               out.data_ptr<double>(), ws.data_ptr<double>(), ws_bytes, stream_of(est)),
+           "vrvq_bss_sdr");
+  return out;
+}
+
 // --------------------------------------------------------------------------- spectral distance
 // The log and magnitude terms of MultiScaleSTFTLoss / MelSpectrogramLoss (models/loss.py:168-401)
 // per row and scale (include/vrvq.h "Spectral distance"). est (R, T) or (R, 1, T), ref (B, T) or
@@ -1621,6 +1663,9 @@ TORCH_LIBRARY(vrvq, m) {
       "signal_metrics(Tensor est, Tensor ref, Tensor? lengths) "
       "-> (Tensor metrics, Tensor moments)");
   m.def(
+      "bss_sdr(Tensor est, Tensor ref, Tensor? lengths, int filter_length, bool zero_mean, "
+      "float? load_diag) -> Tensor");
+  m.def(
       "spectral_distance(Tensor est, Tensor ref, Tensor? lengths, int[] windows, int[] n_mels, "
       "Tensor[] tables, Tensor[] bands, Tensor[] weights, float clamp_eps, float pow, "
       "float log_weight, float mag_weight) -> (Tensor terms, Tensor distance)");
@@ -1711,6 +1756,7 @@ TORCH_LIBRARY(vrvq, m) {
   m.impl("rate_solve_capped", &rate_solve_capped); \
   m.impl("scale_imp_packets", &scale_imp_packets); \
   m.impl("signal_metrics", &signal_metrics); \
+  m.impl("bss_sdr", &bss_sdr); \
   m.impl("spectral_distance", &spectral_distance); \
   m.impl("spectral_distance_grad", &spectral_distance_grad); \
   m.impl("pack_counts", &pack_counts); \

@@ -365,6 +365,17 @@ def signal_metrics(est: torch.Tensor, ref: torch.Tensor,
     return _ops().signal_metrics(est, ref, lengths)
 
 
+def bss_sdr(est: torch.Tensor, ref: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+            filter_length: int = 512, zero_mean: bool = False,
+            load_diag: Optional[float] = None) -> torch.Tensor:
+    """BSS-eval SDR (torchmetrics' signal_distortion_ratio) of every row of est (R, T) or
+    (R, 1, T) against row r % B of ref (B, T) or (B, 1, T), over the first lengths[r % B] samples
+    (int64 (B,), or None for all): float64 (R,), in three launches (four with zero_mean) and
+    without a host sync (include/vrvq.h "BSS SDR")."""
+    return _ops().bss_sdr(est, ref, lengths, int(filter_length), bool(zero_mean),
+                          None if load_diag is None else float(load_diag))
+
+
 def spectral_distance(est: torch.Tensor, ref: torch.Tensor, lengths: Optional[torch.Tensor],
                       windows, n_mels, tables, bands, weights, clamp_eps: float, pow: float,
                       log_weight: float = 1.0,
@@ -653,6 +664,10 @@ def _register_fakes():
         R = est.shape[0]
         return (est.new_empty((R, 4), dtype=torch.float64),
                 est.new_empty((R, 8), dtype=torch.float64))
+
+    @reg("vrvq::bss_sdr")
+    def _(est, ref, lengths, filter_length, zero_mean, load_diag):
+        return est.new_empty((est.shape[0],), dtype=torch.float64)
 
     @reg("vrvq::spectral_distance")
     def _(est, ref, lengths, windows, n_mels, tables, bands, weights, clamp_eps, pow,

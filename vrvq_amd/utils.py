@@ -308,6 +308,47 @@ def signal_metrics(est: torch.Tensor, ref: torch.Tensor, lengths=None) -> dict:
     return out
 
 
+BSS_SDR = "bss_sdr"                    # rd_sweep's column and solve_quality's metric name
+BSS_SDR_MAX_FILTER = 512
+BSS_SDR_MAX_ROWS = 65535               # vrvq_bss_sdr's bound on rows (a grid dimension)
+
+
+def bss_sdr(est: torch.Tensor, ref: torch.Tensor, lengths=None, filter_length: int = 512,
+            zero_mean: bool = False, load_diag=None) -> torch.Tensor:
+    """BSS-eval SDR (dB) of reconstructions against their inputs on the device: the "SDR" of
+    models/utils.py:91-143 cal_metrics, torchmetrics.functional.signal_distortion_ratio (without
+    use_cg_iter), for every row at once and without a host sync (include/vrvq.h "BSS SDR"). The
+    estimate is projected onto the span of the `filter_length` delayed copies of the reference,
+    so a short linear filter between input and output (a delay, a tilt) is forgiven; the ratio is
+    the energy inside that span over the energy outside it, all of it in fp64.
+
+    est is (R, T) or (R, 1, T), ref (B, T) or (B, 1, T) with R = L * B level-major and `lengths`
+    one per clip, as in signal_metrics; `zero_mean` removes each row's mean first, `load_diag` is
+    added to the autocorrelation's lag 0. Returns (L, B) float64. The autocorrelation of a clip
+    is formed once for its L reconstructions, its Levinson recursion once per four of them, and
+    at most 65535 rows go into one call. A silent or empty row, a NaN in its data or a singular
+    system gives NaN; est == ref gives +inf or NaN. Argument errors are ValueErrors before any
+    launch."""
+    for x, what in ((est, "est"), (ref, "ref")):
+        if not torch.is_tensor(x) or x.dim() < 2 or x.numel() == 0 \
+                or x.numel() != x.shape[0] * x.shape[-1]:
+            raise ValueError(f"bss_sdr: {what} must be (rows, T) or (rows, 1, T)")
+    R, B = est.shape[0], ref.shape[0]
+    if ref.shape[-1] != est.shape[-1] or R % B:
+        raise ValueError(f"bss_sdr: est {tuple(est.shape)} against ref {tuple(ref.shape)}")
+    if R > BSS_SDR_MAX_ROWS:
+        raise ValueError(f"bss_sdr: {R} rows; at most {BSS_SDR_MAX_ROWS} in one call")
+    if not 1 <= int(filter_length) <= BSS_SDR_MAX_FILTER:
+        raise ValueError(f"bss_sdr: filter_length {filter_length} is outside "
+                         f"[1, {BSS_SDR_MAX_FILTER}]")
+    out = ops.bss_sdr(est.contiguous(), ref.contiguous(), _clip_lengths(lengths, B, est.device),
+                      int(filter_length), bool(zero_mean), load_diag)
+    return out.reshape(R // B, B)
+
+
+_bss_sdr = bss_sdr                     # rd_sweep has a flag of the function's name
+
+
 # ------------------------------------------------------------------ spectral distances
 SPECTRAL_METRICS = ("mel", "stft")     # distances, smaller is better: rd_sweep columns, solve_quality
 MEL_DISTANCE = dict(windows=(2048, 512), n_mels=(150, 80), clamp_eps=1e-5, pow=2.0,
@@ -528,7 +569,8 @@ def _decoded(model, z_all: torch.Tensor, cap, samples: int, what: str) -> torch.
 
 
 def rd_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_codebook=10,
-             lengths=None, max_decode_clips: int | None = None, spectral=None) -> dict:
+             lengths=None, max_decode_clips: int | None = None, spectral=None,
+             bss_sdr: bool = False) -> dict:
     """Rate-distortion curves of every clip: the table scripts/inference.py:95-122 writes
     (metadata.json, {"sisdr", "kbps"} per level), per clip and with the distortion computed on
     the device.
@@ -549,7 +591,11 @@ def rd_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_codeb
     (mel_distance, the paper's other distortion axis) and / or "stft" (stft_distance): each adds
     an (L, B) float64 entry of that name, computed from the same `recon`, input and `lengths`,
     and its batch mean under the same name in every summary row. They need clips of more than
-    1024 samples."""
+    1024 samples.
+
+    `bss_sdr` (default False: nothing added, nothing more runs) adds "bss_sdr", the BSS-eval SDR
+    (L, B) float64 of the function of that name at its defaults, from the same `recon`, input and
+    `lengths`, and its batch mean under "bss_sdr" in every summary row."""
     _check_vbr_eval(model, "rd_sweep")
     levels = [float(v) for v in levels]
     if not levels:
@@ -568,16 +614,19 @@ def rd_sweep(model, audio: torch.Tensor, levels: Sequence[float], bits_per_codeb
         out = signal_metrics(recon, x, lengths)
         for name in spectral:
             out[name] = _spectral_metric(name, recon, x, model.sample_rate, lengths)
+        if bss_sdr:
+            out[BSS_SDR] = _bss_sdr(recon, x, lengths)
+        extra = spectral + ((BSS_SDR,) if bss_sdr else ())  # (L, B) columns with a summary mean
         bpf = rate_curve(enc["imp_map"], levels, n_q, bits_per_codebook).t().contiguous()
         kbps = bpf.to(torch.float64) * (math.floor(model.sample_rate / model.hop_length) / 1000)
         sisdr_mean, kbps_mean = out["si_sdr"].mean(1), kbps.mean(1)
-        spectral_means = [out[name].mean(1) for name in spectral]
+        extra_means = [out[name].mean(1) for name in extra]
     check_errors(audio.device)  # the sweep's one encode: a timed-out hand-off raises here
     out.update(levels=_device_const(levels, torch.float32, x.device), bpf=bpf, kbps=kbps,
                recon=recon)
     out["summary"] = [{"level": lv, "level_scaled": lv * n_q, "sisdr": s, "kbps": k}
                       for lv, s, k in zip(levels, sisdr_mean.tolist(), kbps_mean.tolist())]
-    for name, means in zip(spectral, spectral_means):
+    for name, means in zip(extra, extra_means):
         for row, v in zip(out["summary"], means.tolist()):
             row[name] = v
     return out
@@ -631,9 +680,9 @@ def _quality_args(model, audio, min_db, metric: str, iters: int) -> torch.Tensor
     q = model.quantizer
     if q.level_min is None or q.level_max is None:
         raise ValueError("solve_quality: the model needs level_min and level_max")
-    if metric not in QUALITY_METRICS + SPECTRAL_METRICS:
+    if metric not in QUALITY_METRICS + (BSS_SDR,) + SPECTRAL_METRICS:
         raise ValueError(f"solve_quality: metric {metric!r} is not one of "
-                         f"{QUALITY_METRICS + SPECTRAL_METRICS}")
+                         f"{QUALITY_METRICS + (BSS_SDR,) + SPECTRAL_METRICS}")
     if int(iters) < 0:
         raise ValueError("solve_quality: iters must be >= 0")
     if metric in SPECTRAL_METRICS and audio.shape[-1] < SPECTRAL_MIN_SAMPLES:
@@ -656,8 +705,9 @@ def _quality_args(model, audio, min_db, metric: str, iters: int) -> torch.Tensor
 def solve_quality(model, audio: torch.Tensor, min_db, metric: str = "si_sdr", iters: int = 8,
                   lengths=None) -> dict:
     """Constant-quality encoding: per clip a level in [level_min, level_max] whose
-    reconstruction reaches `min_db` (a number, or one per clip) in `metric` ("si_sdr", "si_snr"
-    or "snr"), found by bisection with the decoder and the metric in the loop, all on the device.
+    reconstruction reaches `min_db` (a number, or one per clip) in `metric` ("si_sdr", "si_snr",
+    "snr" or "bss_sdr", the BSS-eval SDR of bss_sdr at its defaults), found by bisection with the
+    decoder and the metric in the loop, all on the device.
 
     One encode (codes and the importance map do not depend on the level), one decode of 2 B clips
     for level_max and level_min, then `iters` rounds, each scale_imp_rows -> mask -> masked_sum
@@ -688,7 +738,7 @@ def solve_quality(model, audio: torch.Tensor, min_db, metric: str = "si_sdr", it
     flipped = metric in SPECTRAL_METRICS
     if flipped:
         target = -target
-    else:
+    elif metric != BSS_SDR:
         col = METRICS.index(metric)
     nq, q = model.n_codebooks, model.quantizer
     with torch.no_grad():
@@ -705,6 +755,8 @@ def solve_quality(model, audio: torch.Tensor, min_db, metric: str = "si_sdr", it
             if flipped:  # (L, B) level-major rows -> one value per row, negated: larger is better
                 return recon, -_spectral_metric(metric, recon, x, model.sample_rate,
                                                 lengths).reshape(-1)
+            if metric == BSS_SDR:
+                return recon, ops.bss_sdr(recon, x, lengths)
             return recon, ops.signal_metrics(recon, x, lengths)[0][:, col]
 
         ends = torch.cat([_latents_at(imp, z_q_is, lv, nq)[2] for lv in (level_max, level_min)])
